@@ -142,7 +142,45 @@ def parse():
     ap.add_argument("--lab", action="store_true",
                     help="load the experiments flavour of the library (libsdfhip_lab.so, include/sdfhip_experimental.h): needed by the A/B "
                          "forms --one-kernel and --shadow-queue")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last timed step rendered (what a caller of the path receives; sharded: "
+                         "rank 0's assembled frame) to DIR/frame.npy as float32 -- RGBA32F as rendered, RGBA8 (--display) as its byte values; "
+                         "NaN channels as 0 with their places in DIR/frame_nonfinite.npy; a frame above 64 MB as a fixed sample of its "
+                         "pixels (see dump_frame)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.single_process or args.devices):
+        ap.error("--dump-outputs is not available with --single-process / --devices (the frames stay inside the library)")
+    return args
+
+
+DUMP_LIMIT = 64_000_000                   # bytes --dump-outputs writes at most, .npy headers included
+
+
+def dump_frame(path, img):
+    """--dump-outputs: one frame (H, W, C) as float32 files under path.  Every value written is finite: on some pixels the shader's
+    normalize() of a zero gradient leaves NaN colour channels (the reference's result, which the kernels reproduce bit for bit), and
+    those are written as 0 -- what the display pass's saturate() shows for them -- with frame_nonfinite.npy (H, W) naming each pixel's
+    non-finite channels as a bit mask (channel c: 2**c): every finite value exactly, and the place of every other one.  A frame larger
+    than DUMP_LIMIT allows is written as frame_sample.npy (n, C) and frame_sample_nonfinite.npy (n,) at a fixed set of flat pixel
+    indices (seed 0: the same for every run of the same frame size), and those indices as frame_sample_index.npy (float64, exact)."""
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    bad = ~np.isfinite(img)
+    nonfinite = (bad * (1 << np.arange(img.shape[-1]))).sum(-1).astype(np.float32)
+    img = np.where(bad, np.float32(0), img)
+    room = DUMP_LIMIT - 1024                # (a .npy header is 128 bytes)
+    if img.nbytes + nonfinite.nbytes <= room:
+        np.save(os.path.join(path, "frame.npy"), img)
+        np.save(os.path.join(path, "frame_nonfinite.npy"), nonfinite)
+        return
+    px = img.reshape(img.shape[0] * img.shape[1], -1)
+    n = room // (px.shape[1] * 4 + 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(path, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(path, "frame_sample_nonfinite.npy"), nonfinite.reshape(-1)[idx])
+    np.save(os.path.join(path, "frame_sample_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -680,6 +718,11 @@ def main():
     drain()
     barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame, before any later pass reuses its buffer (the barrier above has completed it)
+        group, within = divmod(args.steps - 1, G)
+        img = (frame if sharded else local)[group % nbuf][within].cpu().numpy()
+        dump_frame(args.dump_outputs, img.view(np.uint8).reshape(H, W, 4) if args.display else img)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if nccl else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

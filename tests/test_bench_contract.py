@@ -158,6 +158,57 @@ def test_bench_ab_forms_need_the_experiments_flavour():
     assert out.returncode != 0 and "--lab" in (out.stderr + out.stdout)
 
 
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_frame(tmp_path):
+    # --dump-outputs: the frame of the last timed step, as the caller gets it -- the oracle's frame of the same scene and camera, bit for
+    # bit, its NaN channels (16 pixels of this frame: normalize() of a zero gradient) written as 0 and marked in frame_nonfinite.npy
+    import numpy as np
+    import oracle
+    import sdfbox_amd as sb
+    from bench_configs import bench_camera
+    from conftest import assert_frames_identical
+    W, H = 320, 200
+    od = sb.dragon_standin(6)
+    oracle.build()
+    ref, _ = oracle.render(od.Structs, od.Values, bench_camera(sb, W, H).State, W, H)
+    bad = ~np.isfinite(ref)
+    assert bad.any()
+    # the frame as rendered, and as rank 0 assembles it from the shares of the sharded pipeline (one rank, 4 frames per gather)
+    for name, extra in (("plain", []), ("sharded", ["--exercise-gather"])):
+        j = run_bench("--steps", 7, "--warmup", 1, "--depth", 6, "--size", f"{W}x{H}", "--no-cpu-baseline", "--dump-outputs", tmp_path / name, *extra)
+        assert j["steps"] == 7 and j["config"]["frames_rendered_in_the_timed_region"] == 7 and j["ms_per_step"] > 0
+        got, nonfinite = np.load(tmp_path / name / "frame.npy"), np.load(tmp_path / name / "frame_nonfinite.npy")
+        assert got.dtype == nonfinite.dtype == np.float32 and got.shape == (H, W, 4) and nonfinite.shape == (H, W)
+        assert np.isfinite(got).all() and np.isfinite(nonfinite).all()
+        assert_frames_identical(got, np.where(bad, np.float32(0), ref), f"bench.py --dump-outputs ({name})")
+        assert (nonfinite == (bad * np.array([1, 2, 4, 8])).sum(-1)).all(), name
+
+
+def test_dump_outputs_writes_finite_values_and_a_fixed_sample_of_a_large_frame(tmp_path, monkeypatch):
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import bench
+    img = np.arange(40 * 30 * 4, dtype=np.float32).reshape(40, 30, 4)
+    img[3, 5, :3] = np.nan
+    img[7, 1, 2] = np.inf
+    want = (~np.isfinite(img) * np.array([1, 2, 4, 8])).sum(-1)
+    bench.dump_frame(str(tmp_path / "small"), img)
+    got, nonfinite = np.load(tmp_path / "small" / "frame.npy"), np.load(tmp_path / "small" / "frame_nonfinite.npy")
+    assert (got == np.where(np.isfinite(img), img, 0)).all() and (nonfinite == want).all()
+    assert nonfinite[3, 5] == 7 and nonfinite[7, 1] == 4 and (nonfinite != 0).sum() == 2
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 8192)
+    for d in ("a", "b"):
+        bench.dump_frame(str(tmp_path / d), img)
+        assert not (tmp_path / d / "frame.npy").exists()
+    px, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_index.npy")
+    nf = np.load(tmp_path / "a" / "frame_sample_nonfinite.npy")
+    assert px.dtype == nf.dtype == np.float32 and idx.dtype == np.float64 and len(px) == len(idx) == len(nf) > 200
+    assert sum(os.path.getsize(f) for f in (tmp_path / "a").iterdir()) <= 8192
+    i = idx.astype(np.int64)
+    assert (px == np.where(np.isfinite(img), img, 0).reshape(-1, 4)[i]).all() and (nf == want.reshape(-1)[i]).all() and (np.diff(idx) > 0).all()
+    assert (idx == np.load(tmp_path / "b" / "frame_sample_index.npy")).all()              # the same pixels every run
+
+
 def test_roofline_reports_only_measured_fractions():
     # bench.py's roofline(): `frac` is the fraction SURVEY.md 8d asks for -- HBM counter bytes / time / 8 TB/s (bound "hbm") --
     # with the issued-VALU fraction of the chip's spec rate as its PEER and `limiting` naming the larger; fractions of the
