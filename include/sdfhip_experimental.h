@@ -49,43 +49,10 @@ enum {
     SDFHIP_TUNE_PERSISTENT_WAVES = 0x400000
 };
 
-/* ---- round 1 / round 2 gather formats (superseded by the sparse shares the march kernel writes, sdfhip_render_sparse_device) */
+/* ---- round 1's gather format (superseded by the sparse shares the march kernel writes, sdfhip_render_sparse_device) ------- */
 /* sdfhip_deinterleave_device / _bands_device of this library also accept pixel_bytes = 5: d_gathered then holds the wire
  * buffers SDFHIP_FLAG_WIRE renders make, and d_frame receives the RGBA32F frame, bit for bit what a render without the flag
  * writes. */
-
-/* Sparse wire format: what the ranks put on xGMI when most of a frame is sky.  A frame-share in the
- * wire format of SDFHIP_FLAG_WIRE (rows x width pixels, rows a multiple of 8) is compacted on its own
- * GPU -- the code bytes stay; of the float plane only the values with any bit set, packed in tile
- * order behind a 64-bit mask and a slot index per 8x8 tile -- gathered, and expanded by rank 0 while it
- * restores row order.  `capacity` = float slots per frame-share; a share with more lit pixels sets the
- * overflow word (then the frame is not complete: choose the capacity from a measured maximum, or
- * rows * width to be safe).  Lossless within the capacity; 1.2 bytes per pixel + 4 per lit pixel.
- *   sdfhip_wire_sparse_bytes            bytes of one sparse frame-share
- *   sdfhip_wire_compact_device          d_wire [frames] dense wire shares -> d_sparse [frames] sparse shares
- *   sdfhip_deinterleave_sparse_device   like sdfhip_deinterleave[_bands]_device (owner may be NULL: round
- *                                       robin) for [world][frames] sparse shares; *d_overflow (device word,
- *                                       may be NULL) is OR-ed with 1 when a share overflowed */
-SDFHIP_API uint64_t sdfhip_wire_sparse_bytes(uint32_t width, uint32_t rows, uint32_t capacity);
-/* Recovery when a sparse share overflowed its capacity: byte offset, within a sparse share, of its 16-byte
- * header {uint32 lit pixels, uint32 overflowed, 0, 0} -- the sender reads word 1 of its own shares and rank 0
- * that of the gathered ones, and the rank concerned sends the share again in the dense wire format
- * (point to point: no other rank takes part), which rank 0 writes over that rank's rows with
- *   sdfhip_deinterleave_share_device   like sdfhip_deinterleave[_bands]_device, but d_share holds the
- *                                      [frames] buffers of ONE rank (`rank`) and only its rows are written
- * (owner may be NULL: round robin). */
-SDFHIP_API uint64_t sdfhip_wire_sparse_head_offset(uint32_t width, uint32_t rows, uint32_t capacity);
-SDFHIP_API int sdfhip_deinterleave_share_device(int device, const void *d_share, void *d_frame,
-                                                uint32_t width, uint32_t height, uint32_t band_rows,
-                                                uint32_t world, uint32_t rows_per_rank, const uint8_t *owner,
-                                                uint32_t rank, uint32_t pixel_bytes, uint32_t frames, void *stream);
-SDFHIP_API int sdfhip_wire_compact_device(int device, const void *d_wire, void *d_sparse, uint32_t width,
-                                          uint32_t rows, uint32_t frames, uint32_t capacity, void *stream);
-SDFHIP_API int sdfhip_deinterleave_sparse_device(int device, const void *d_gathered, void *d_frame,
-                                                 uint32_t width, uint32_t height, uint32_t band_rows,
-                                                 uint32_t world, uint32_t rows_per_rank, const uint8_t *owner,
-                                                 uint32_t capacity, uint32_t frames, uint32_t *d_overflow,
-                                                 void *stream);
 
 /* ---- test hooks ----------------------------------------------------------------------------------------------------------- */
 /* Test hook: how many packed floats the next share of every device carries (normally 1.25 x what its last share used; 0 = all

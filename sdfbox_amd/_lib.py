@@ -231,13 +231,6 @@ _SIG = {
 }
 # include/sdfhip_experimental.h: exported by the experiments flavour only
 _SIG_LAB = {
-    "sdfhip_wire_sparse_bytes": (_c.c_uint64, [_c.c_uint32, _c.c_uint32, _c.c_uint32]),
-    "sdfhip_wire_sparse_head_offset": (_c.c_uint64, [_c.c_uint32, _c.c_uint32, _c.c_uint32]),
-    "sdfhip_deinterleave_share_device": (_c.c_int, [_c.c_int, _vp, _vp, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
-                                                    _c.c_uint32, _c.POINTER(_c.c_uint8), _c.c_uint32, _c.c_uint32, _c.c_uint32, _vp]),
-    "sdfhip_wire_compact_device": (_c.c_int, [_c.c_int, _vp, _vp, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _vp]),
-    "sdfhip_deinterleave_sparse_device": (_c.c_int, [_c.c_int, _vp, _vp, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
-                                                     _c.c_uint32, _c.POINTER(_c.c_uint8), _c.c_uint32, _c.c_uint32, _vp, _vp]),
     "sdfhip_debug_tile_order": (_c.c_int, [_vp, _vp, _vp]),
     "sdfhip_debug_unorm_table": (_c.c_int, [_c.c_int, _vp]),
     "sdfhip_debug_step_classes": (_c.c_int, [_vp, _vp, _c.POINTER(_c.c_uint64)]),

@@ -12,7 +12,6 @@
 
 #include <atomic>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 
 using namespace sdfhip;
@@ -189,86 +188,6 @@ int sdfhip::launch_experiment(sdfhip_scene *s, const RenderCall &c, RenderParams
     *launched = true;
     return SDFHIP_OK;
 }
-
-extern "C" int sdfhip_deinterleave_share_device(int device, const void *d_share, void *d_frame,
-                                                uint32_t width, uint32_t height, uint32_t band_rows,
-                                                uint32_t world, uint32_t rows_per_rank, const uint8_t *owner,
-                                                uint32_t rank, uint32_t pixel_bytes, uint32_t frames, void *stream)
-try {
-    return sdfhip::deinterleave_impl(device, d_share, d_frame, width, height, band_rows, world, rows_per_rank, owner,
-                             pixel_bytes, frames, stream, rank);
-}
-SDFHIP_ABI_CATCH(sdfhip_deinterleave_share_device)
-
-extern "C" uint64_t sdfhip_wire_sparse_bytes(uint32_t width, uint32_t rows, uint32_t capacity)
-try {
-    return (uint64_t)sparse_layout(width, rows, capacity).bytes;
-}
-SDFHIP_ABI_CATCH_AS(sdfhip_wire_sparse_bytes, 0)
-
-extern "C" uint64_t sdfhip_wire_sparse_head_offset(uint32_t width, uint32_t rows, uint32_t capacity)
-try {
-    return (uint64_t)sparse_layout(width, rows, capacity).off_head;
-}
-SDFHIP_ABI_CATCH_AS(sdfhip_wire_sparse_head_offset, 0)
-
-extern "C" int sdfhip_wire_compact_device(int device, const void *d_wire, void *d_sparse, uint32_t width, uint32_t rows,
-                                          uint32_t frames, uint32_t capacity, void *stream)
-try {
-    if (!d_wire || !d_sparse || width == 0 || rows == 0 || frames == 0)
-        return fail(SDFHIP_ERR_ARG, "wire_compact: null or zero argument");
-    if (((size_t)rows * width) % 4 != 0) return fail(SDFHIP_ERR_ARG, "wire_compact: rows * width must be a multiple of 4");
-    DeviceGuard g(device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "wire_compact: hipSetDevice(%d) failed", device);
-    const SparseLayout L = sparse_layout(width, rows, capacity);
-    const dim3 grid((L.tiles + 3) / 4, frames);
-    hipLaunchKernelGGL(k_sparse_masks, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t *)d_wire, (uint8_t *)d_sparse, L);
-    hipLaunchKernelGGL(k_sparse_scan, dim3(frames), dim3(1024), 0, (hipStream_t)stream, (uint8_t *)d_sparse, L);
-    hipLaunchKernelGGL(k_sparse_scatter, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t *)d_wire, (uint8_t *)d_sparse, L);
-    HIP_TRY(hipGetLastError());
-    return SDFHIP_OK;
-}
-SDFHIP_ABI_CATCH(sdfhip_wire_compact_device)
-
-extern "C" int sdfhip_deinterleave_sparse_device(int device, const void *d_gathered, void *d_frame, uint32_t width,
-                                                 uint32_t height, uint32_t band_rows, uint32_t world,
-                                                 uint32_t rows_per_rank, const uint8_t *owner, uint32_t capacity,
-                                                 uint32_t frames, uint32_t *d_overflow, void *stream)
-try {
-    if (frames == 0 || !d_gathered || !d_frame || width == 0 || height == 0 || band_rows == 0 || world == 0)
-        return fail(SDFHIP_ERR_ARG, "deinterleave_sparse: null or zero argument");
-    if (band_rows % 8 != 0 || rows_per_rank % 8 != 0)
-        return fail(SDFHIP_ERR_ARG, "deinterleave_sparse: bands must be whole 8x8 tiles (band_rows %u, rows_per_rank %u)", band_rows, rows_per_rank);
-    const uint32_t nbands = (height + band_rows - 1) / band_rows;
-    BandMap M;
-    M.n = 0;
-    memset(M.src, 0, sizeof M.src);
-    uint32_t need_rows = ((nbands + world - 1) / world) * band_rows;
-    if (owner) {
-        if (nbands > (uint32_t)MAX_BAND_LIST || world > 64)
-            return fail(SDFHIP_ERR_ARG, "deinterleave_sparse: %u bands (max %d) over %u ranks (max 64)", nbands, MAX_BAND_LIST, world);
-        uint32_t have[64] = { 0 };
-        for (uint32_t b = 0; b < nbands; b++) {
-            if (owner[b] >= world) return fail(SDFHIP_ERR_ARG, "deinterleave_sparse: band %u belongs to rank %u of %u", b, (unsigned)owner[b], world);
-            M.src[b] = (uint16_t)((uint32_t)owner[b] << 10 | have[owner[b]]++);
-        }
-        M.n = nbands;
-        need_rows = 0;
-        for (uint32_t r = 0; r < world; r++) need_rows = have[r] * band_rows > need_rows ? have[r] * band_rows : need_rows;
-    }
-    if (rows_per_rank < need_rows)
-        return fail(SDFHIP_ERR_ARG, "deinterleave_sparse: rows_per_rank %u < %u needed", rows_per_rank, need_rows);
-    DeviceGuard g(device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "deinterleave_sparse: hipSetDevice(%d) failed", device);
-    const SparseLayout L = sparse_layout(width, rows_per_rank, capacity);
-    size_t total = (size_t)width * height * frames;
-    uint32_t blocks = (uint32_t)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(k_deinterleave_sparse, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)d_gathered,
-                       (float4 *)d_frame, width, height, band_rows, world, frames, L, M, d_overflow);
-    HIP_TRY(hipGetLastError());
-    return SDFHIP_OK;
-}
-SDFHIP_ABI_CATCH(sdfhip_deinterleave_sparse_device)
 
 extern "C" int sdfhip_debug_tile_order(sdfhip_scene *s, const uint32_t *d_perm, uint16_t *d_cost)
 try {

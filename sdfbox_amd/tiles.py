@@ -3,33 +3,34 @@ reference is single-GPU: SURVEY.md 8e).
 
 Pixels are independent and the scene is read-only, so the octree is replicated
 on every device and the *frame* is sharded: row bands of `band_rows` rows are
-dealt round-robin (band b -> rank b mod world), which balances sky against
-object rows.  Each rank renders its bands into a compact local buffer of
-`rows_per_rank` rows; one gather per frame brings the buffers to rank 0 over
-xGMI (RCCL send/recv: every peer has its own direct link into rank 0), where
-a small kernel restores row order.  No other collective is on the data path.
+dealt to the ranks (`BandLayout`: round robin, band b -> rank b mod world, or an
+explicit `owner` list such as `balanced_owner` deals from the measured cost of
+every band, `band_costs`).  Each rank renders its bands into a compact local
+buffer of `rows_per_rank` rows; one gather per frame, or per group of frames
+(`group_plan`), brings the buffers to rank 0 over xGMI (RCCL send/recv: every
+peer has its own direct link into rank 0), where a small kernel restores row
+order.  No other collective is on the data path.
 
-The gather is bound by one xGMI link per peer (frame bytes / world over ~77 GB/s
-per direction), and at ~8 Gray/s per GPU an RGBA32F frame would make every
-world size link-bound.  Every pixel the shader writes is (a, a, a, steps) or the
-sky constant, so ranks render 5-byte *wire pixels* (FLAG_WIRE: per frame a plane
-of floats -- the bits of a -- followed by a plane of bytes -- the step count, or
-255 minus it for a sky pixel; `wire_shape`) and rank 0 expands them while restoring
-row order -- the assembled RGBA32F frame is bit for bit the single-GPU frame.
+A rank's buffer is either dense -- RGBA32F frames, or RGBA8 ones from the fused
+display pass (`render_bands`, `render_bands_batch`), which rank 0 reorders with
+`deinterleave` -- or a *sparse share* that the march kernel writes itself
+(`render_sparse2`, or `SparseShareCall` for a renderer that launches the same
+share frame after frame): per 8x8 tile a mask of the pixels whose grey level has
+any bit set, the tile's 64 code bytes, and those grey levels packed in slots
+behind a counter -- about 1.1-1.5 bytes per pixel instead of 16.  Rank 0 expands the
+shares in row order with `deinterleave_sparse2` (or `SparseExpandCall`); the
+assembled frame is bit for bit the single-GPU frame.  A gather carries a fixed
+number of floats per share: a rank whose share needed more sends the rest of its
+float tail point to point, and rank 0 then expands that rank's rows again
+(`only_rank`).
 
-Most of a wire float plane is zeros (sky and unlit pixels), so before the gather a
-rank may compact its shares into the *sparse* wire format (`wire_compact`: code
-bytes, per 8x8 tile a mask and a slot index, the non-zero floats packed; about
-1.2 bytes per pixel + 4 per lit pixel) and rank 0 expands that instead
-(`deinterleave_sparse`).  The capacity of the float array is fixed per run: choose
-it from a measured maximum (`sparse_count`).  A share with more lit pixels than that
-says so in its header (`sparse_headers`): its rank then sends the dense wire share
-as well, point to point, and rank 0 writes it over that rank's rows
-(`deinterleave_share`) -- the frame is complete either way.
+The laboratory library also keeps round 1's dense *wire* form for A/B runs:
+5-byte pixels (FLAG_WIRE renders, `wire_shape`) that `deinterleave` expands to
+RGBA32F with `pixel_bytes=5`.
 """
 import ctypes
 
-from ._lib import check, lib, need_lab
+from ._lib import check, lib
 
 
 class BandLayout:
@@ -230,70 +231,6 @@ def deinterleave(device, gathered_ptr, frame_ptr, width, layout, stream=None, pi
                                          ctypes.c_void_p(int(frame_ptr)), int(width),
                                          layout.height, layout.band_rows, layout.world,
                                          layout.rows_per_rank, int(pixel_bytes), int(frames), st))
-
-
-def sparse_share_bytes(rows, width, capacity):
-    """Bytes of one frame-share in the sparse wire format."""
-    need_lab("sparse_share_bytes")
-    return int(lib.sdfhip_wire_sparse_bytes(int(width), int(rows), int(capacity)))
-
-
-def wire_compact(device, wire_ptr, sparse_ptr, width, rows, frames, capacity, stream=None):
-    """[frames] dense wire shares (FLAG_WIRE renders) -> [frames] sparse shares, on `stream`."""
-    need_lab("wire_compact")
-    check(lib.sdfhip_wire_compact_device(int(device), ctypes.c_void_p(int(wire_ptr)), ctypes.c_void_p(int(sparse_ptr)),
-                                         int(width), int(rows), int(frames), int(capacity),
-                                         ctypes.c_void_p(int(stream)) if stream else None))
-
-
-def sparse_head_offset(rows, width, capacity):
-    """Byte offset of a sparse share's header {uint32 lit pixels, uint32 overflowed, 0, 0}."""
-    need_lab("sparse_head_offset")
-    return int(lib.sdfhip_wire_sparse_head_offset(int(width), int(rows), int(capacity)))
-
-
-def sparse_headers(sparse_tensor, rows, width, capacity):
-    """The headers of the sparse shares in a uint8 tensor [..., sparse_share_bytes], as a strided uint8 view
-    [..., 8] (lit pixels, overflowed) -- to be copied to pinned host memory behind the stream that made them."""
-    off = sparse_head_offset(rows, width, capacity)
-    return sparse_tensor[..., off:off + 8]
-
-
-def deinterleave_share(device, share_ptr, frame_ptr, width, layout, rank, stream=None, pixel_bytes=5, frames=1):
-    """Rank 0: write ONE rank's buffers ([frames] x rows_per_rank x width pixels; pixel_bytes as for
-    `deinterleave`) over that rank's rows of the frames: the dense resend of a share whose sparse form
-    overflowed its capacity."""
-    need_lab("deinterleave_share")
-    owner = (ctypes.c_uint8 * layout.n_bands)(*layout.owner) if layout.weighted else None
-    check(lib.sdfhip_deinterleave_share_device(int(device), ctypes.c_void_p(int(share_ptr)), ctypes.c_void_p(int(frame_ptr)),
-                                               int(width), layout.height, layout.band_rows, layout.world,
-                                               layout.rows_per_rank, owner, int(rank), int(pixel_bytes), int(frames),
-                                               ctypes.c_void_p(int(stream)) if stream else None))
-
-
-def sparse_count(sparse_tensor, rows, width, capacity):
-    """Lit pixels (float slots needed) and overflow flag of every sparse share in a uint8 tensor
-    [..., sparse_share_bytes]: -> (counts, overflowed) as flat lists.  Synchronises."""
-    import torch
-    nbytes = sparse_share_bytes(rows, width, capacity)
-    off_head = sparse_head_offset(rows, width, capacity)
-    flat = sparse_tensor.reshape(-1, nbytes)
-    head = flat[:, off_head:off_head + 8].contiguous().cpu().view(torch.int32)
-    return head[:, 0].tolist(), head[:, 1].tolist()
-
-
-def deinterleave_sparse(device, gathered_ptr, frame_ptr, width, layout, capacity, stream=None, frames=1, overflow_ptr=None):
-    """Rank 0: gathered sparse shares (world x frames x sparse_share_bytes) -> frames x height x width
-    RGBA32F.  overflow_ptr: a device int32 that is OR-ed with 1 if a share had more lit pixels than
-    `capacity` (the frame is then incomplete)."""
-    need_lab("deinterleave_sparse")
-    owner = (ctypes.c_uint8 * layout.n_bands)(*layout.owner) if layout.weighted else None
-    check(lib.sdfhip_deinterleave_sparse_device(int(device), ctypes.c_void_p(int(gathered_ptr)),
-                                                ctypes.c_void_p(int(frame_ptr)), int(width), layout.height,
-                                                layout.band_rows, layout.world, layout.rows_per_rank, owner,
-                                                int(capacity), int(frames),
-                                                ctypes.c_void_p(int(overflow_ptr)) if overflow_ptr else None,
-                                                ctypes.c_void_p(int(stream)) if stream else None))
 
 
 # ---- sparse shares written by the march kernel itself (sdfhip_render_sparse_device) ----------------------------

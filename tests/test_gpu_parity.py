@@ -699,69 +699,15 @@ def od_depth(sb, od):
         return sc.depth
 
 
-def test_sparse_wire_format_is_lossless_within_its_capacity(sb, gpu_scenes):
+def test_wire_expansion_on_random_shares(sb):
     lab_only(sb)
-    # dense wire shares compacted on the rendering side (codes + per-tile mask and slot index + packed
-    # non-zero floats), expanded by the rank-0 kernel: the same frame bit for bit; too small a
-    # capacity is reported, never silent
+    # round 1's wire format (5-byte pixels, pixel_bytes = 5) fed with arbitrary shares -- any float bit pattern: NaNs, -0.0,
+    # denormals; any legal code byte; ragged widths -- against the rule on the host (wire_expand): a code above 140 is the sky
+    # constant with 255 - code steps, any other is (a, a, a, code); rows come from BandLayout.source_of.  Bit for bit.
     import torch
-    BandLayout, deinterleave_sparse, render_bands_batch, sparse_count, sparse_share_bytes, wire_compact, wire_shape = (sb.tiles.BandLayout, sb.tiles.deinterleave_sparse, sb.tiles.render_bands_batch, sb.tiles.sparse_count, sb.tiles.sparse_share_bytes, sb.tiles.wire_compact, sb.tiles.wire_shape)
+    BandLayout, deinterleave, wire_shape = sb.tiles.BandLayout, sb.tiles.deinterleave, sb.tiles.wire_shape
     stream = torch.cuda.current_stream().cuda_stream
-    scene = gpu_scenes["torus_d6"]
-    for (W, H, world, band_rows, w0) in [(160, 96, 1, 96, 1.0), (150, 90, 3, 16, 1.0), (97, 61, 4, 8, 0.6), (64, 200, 8, 8, 0.5)]:
-        lay = BandLayout(H, world, band_rows, w0)
-        R = lay.rows_per_rank
-        cams = [make_camera(n, W, H) for n in ("default", "rotated", "closeup")]
-        for i, v in enumerate((0.9, 0.1, 0.2)):
-            cams[1].State.light[i] = v
-        full = [torch.from_numpy(scene.Draw(c, W, H)).cuda() for c in cams]
-        dense = torch.zeros((world, 3) + wire_shape(R, W), dtype=torch.uint8, device="cuda")
-        for r in range(world):
-            render_bands_batch(scene, cams, W, lay, r, dense[r].data_ptr(), flags=sb.FLAG_WIRE, stream=stream)
-        # generous capacity: every pixel could be lit
-        cap = R * W
-        nb = sparse_share_bytes(R, W, cap)
-        sparse = torch.zeros((world, 3, nb), dtype=torch.uint8, device="cuda")
-        for r in range(world):
-            wire_compact(0, dense[r].data_ptr(), sparse[r].data_ptr(), W, R, 3, cap, stream=stream)
-        frames = torch.full((3, H, W, 4), -1.0, dtype=torch.float32, device="cuda")
-        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-        deinterleave_sparse(0, sparse.data_ptr(), frames.data_ptr(), W, lay, cap, stream=stream, frames=3, overflow_ptr=flag.data_ptr())
-        torch.cuda.synchronize()
-        assert int(flag.item()) == 0
-        for f in range(3):
-            assert torch.equal(frames[f].view(torch.int32), full[f].view(torch.int32)), (W, H, world, f)
-        counts, over = sparse_count(sparse, R, W, cap)
-        assert not any(over)
-        # the counts are the pixels whose grey level has any bit set
-        lit = sum(int((fr[..., 0].view(torch.int32) != 0).logical_and(fr[..., 0].view(torch.int32) == fr[..., 1].view(torch.int32)).sum())
-                  for fr in full)      # bitwise: a NaN grey is a lit pixel too
-        assert sum(counts) == lit, (sum(counts), lit)
-        # exactly enough capacity works, one slot less is flagged
-        tight = max(counts)
-        if tight > 1:
-            for capn, expect in ((tight, 0), (tight - 1, 1)):
-                nb2 = sparse_share_bytes(R, W, capn)
-                sp2 = torch.zeros((world, 3, nb2), dtype=torch.uint8, device="cuda")
-                for r in range(world):
-                    wire_compact(0, dense[r].data_ptr(), sp2[r].data_ptr(), W, R, 3, capn, stream=stream)
-                flag.zero_()
-                deinterleave_sparse(0, sp2.data_ptr(), frames.data_ptr(), W, lay, capn, stream=stream, frames=3, overflow_ptr=flag.data_ptr())
-                torch.cuda.synchronize()
-                assert int(flag.item()) == expect, (capn, tight)
-                if not expect:
-                    for f in range(3):
-                        assert torch.equal(frames[f].view(torch.int32), full[f].view(torch.int32))
-                    assert sparse_share_bytes(R, W, capn) < 5 * R * W or tight > R * W * 0.9
-
-
-def test_sparse_wire_format_on_random_shares(sb):
-    lab_only(sb)
-    # the format itself, fed with arbitrary wire shares (any float bit pattern: NaNs, -0.0, denormals;
-    # any legal code byte; ragged widths): expanding the sparse form equals expanding the dense form
-    import torch
-    BandLayout, deinterleave, deinterleave_sparse, sparse_count, sparse_share_bytes, wire_compact, wire_shape = (sb.tiles.BandLayout, sb.tiles.deinterleave, sb.tiles.deinterleave_sparse, sb.tiles.sparse_count, sb.tiles.sparse_share_bytes, sb.tiles.wire_compact, sb.tiles.wire_shape)
-    stream = torch.cuda.current_stream().cuda_stream
+    sky_bits = torch.tensor([0.005, 0.01, 0.2], dtype=torch.float32).view(torch.int32)
     g = torch.Generator(device="cpu").manual_seed(5)
     for (W, H, world, band_rows, frames, p_lit) in [(61, 40, 1, 8, 2, 0.3), (200, 64, 2, 16, 3, 0.05), (33, 96, 4, 8, 1, 0.9), (128, 24, 3, 8, 2, 0.0)]:
         lay = BandLayout(H, world, band_rows)
@@ -777,20 +723,19 @@ def test_sparse_wire_format_on_random_shares(sb):
         dense[:, :, :4] = bits.view(world, frames, R * W).view(torch.uint8).reshape(world, frames, 4, R, W)
         dense[:, :, 4] = codes.to(torch.uint8).view(world, frames, R, W)
         dense = dense.cuda()
-        want = torch.zeros((frames, H, W, 4), dtype=torch.float32, device="cuda")
-        deinterleave(0, dense.data_ptr(), want.data_ptr(), W, lay, stream=stream, pixel_bytes=5, frames=frames)
-        cap = R * W
-        sparse = torch.zeros((world, frames, sparse_share_bytes(R, W, cap)), dtype=torch.uint8, device="cuda")
-        for r in range(world):
-            wire_compact(0, dense[r].data_ptr(), sparse[r].data_ptr(), W, R, frames, cap, stream=stream)
         got = torch.full((frames, H, W, 4), -1.0, dtype=torch.float32, device="cuda")
-        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-        deinterleave_sparse(0, sparse.data_ptr(), got.data_ptr(), W, lay, cap, stream=stream, frames=frames, overflow_ptr=flag.data_ptr())
+        deinterleave(0, dense.data_ptr(), got.data_ptr(), W, lay, stream=stream, pixel_bytes=5, frames=frames)
         torch.cuda.synchronize()
-        assert int(flag.item()) == 0
-        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (W, H, world)
-        counts, _ = sparse_count(sparse, R, W, cap)
-        assert sum(counts) == int((bits != 0).sum())
+        # the host's expansion: [frames][H][W] of a and code, each frame row taken from its rank's local row
+        src = [lay.source_of(y) for y in range(H)]
+        ranks, rows = torch.tensor([r for r, _ in src]), torch.tensor([l for _, l in src])
+        a = bits.view(world, frames, R, W).transpose(0, 1)[:, ranks, rows]
+        code = codes.view(world, frames, R, W).transpose(0, 1)[:, ranks, rows]
+        is_sky = code > 140
+        want = torch.stack([torch.where(is_sky, sky_bits[c], a) for c in range(3)] +
+                           [torch.where(is_sky, 255 - code, code).to(torch.float32).view(torch.int32)], dim=-1)
+        assert torch.equal(got.cpu().view(torch.int32), want), (W, H, world)
+        assert is_sky.any() and not is_sky.all()                   # both rules were exercised
 
 
 def test_two_handles_render_concurrently(sb, oracle_mod, scenes):
