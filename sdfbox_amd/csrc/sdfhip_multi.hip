@@ -396,10 +396,12 @@ int prepare_slot(sdfhip_multi *m, Slot &S, uint32_t n_frames, bool path, bool in
             if (r > 0) { int rc = grow(&B.d_bands, &B.bands_cap, (size_t)n_frames * L.rows_per_rank * L.width * frame_px_bytes, B.stream); if (rc) return rc; }
         } else {
             const ShareShape sh = share_shape(m, n_frames);
-            const uint8_t *before = B.d_share;
+            // a new buffer is told by its capacity, not its address: the allocator may hand the freed smaller buffer's address
+            // back, and that buffer's counter and count_base would then be taken for the new one's
+            const size_t cap_before = B.share_cap;
             int rc = grow(&B.d_share, &B.share_cap, sh.bytes, B.stream);
             if (rc) return rc;
-            if (B.d_share != before || S.dirty) {                       // a new buffer: its counter starts at zero (and is never zeroed again)
+            if (B.share_cap != cap_before || S.dirty) {                 // a new buffer: its counter starts at zero (and is never zeroed again)
                 M_TRY(hipMemsetAsync(B.d_share, 0, 64, B.stream));
                 B.count_base = 0;
             }

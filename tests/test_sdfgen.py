@@ -135,6 +135,69 @@ def test_gpu_builder_equals_oracle(sb, oracle_mod, cloud, depth, form, monkeypat
     assert od.validate() == (int(levels_of(od.Structs).max()), True)
 
 
+# Exact ties.  Every search of the builder keeps the reference's strict `<` scan: of equal distances the earliest list position
+# wins (the segments' 64-bit atomic minima of {distance bits, position}, the sub_min shuffles and the sibling-block butterfly).
+# Only exact duplicates tie bit for bit after the cloud's transform, so every point gets a copy with the OPPOSITE normal: the
+# sign of a corner value comes from the winner's normal, and a builder that picked another of the tied points would change the
+# bytes.  Orders: the copies far behind the originals (the tie crosses 1 024-entry segments and 256-entry LDS chunks), the two
+# interleaved (one wavefront), three copies, and a random choice per point of which copy comes first (the two blocks far apart).
+TIE_ORDERS = ("behind", "interleaved", "triplicates", "mixed")
+
+
+def tie_cloud(base, order, swapped=False):
+    a, b = base, base.copy()
+    b[:, 3:] *= -1
+    if swapped:
+        a, b = b, a
+    if order == "behind":
+        return np.concatenate([a, b])
+    if order == "interleaved":
+        return np.stack([a, b], 1).reshape(-1, 6)
+    if order == "triplicates":
+        return np.concatenate([a, b, a])
+    first = np.random.default_rng(len(base)).random(len(base)) < 0.5
+    return np.concatenate([np.where(first[:, None], a, b), np.where(first[:, None], b, a)])
+
+
+_tie_refs = {}
+
+
+def tie_reference(oracle_mod, cloud, order, swapped, depth):
+    # (the oracle's trees, shared by both flavours of the library)
+    key = (cloud, order, swapped, depth)
+    if key not in _tie_refs:
+        base = {"sphere": fib_sphere(6000), "torus": torus_cloud(8000)}[cloud]
+        v = tie_cloud(base, order, swapped)
+        _tie_refs[key] = (v, oracle_mod.sdfgen(v, depth))
+    return _tie_refs[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["default", "sibling blocks everywhere"])
+@pytest.mark.parametrize("cloud", ["sphere", "torus"])
+def test_gpu_builder_breaks_exact_ties_like_the_oracle(sb, oracle_mod, cloud, form, monkeypatch):
+    # lists of 12 000 - 24 000 entries at the root: the segment kernels take them in 12 - 24 segments (default form), and the
+    # sibling-block kernels in chunks of 256 from level 1 on (SDFHIP_GEN_WIDE=8, the laboratory library)
+    if form != "default":
+        import sdfbox_amd.lab
+        sb = sdfbox_amd.lab.load()
+        monkeypatch.setenv("SDFHIP_GEN_WIDE", "8")
+    for depth in (4, 5, 6, 7):
+        for order in TIE_ORDERS:
+            for swapped in (False, True):
+                v, o = tie_reference(oracle_mod, cloud, order, swapped, depth)
+                what = f"{cloud} depth {depth}, copies {order}{', swapped' if swapped else ''}"
+                od, st = sb.OctData.SdfGen(v, depth, want_stats=True)
+                assert od.Length == len(o["structs"]) == st.nodes, what
+                assert (od.Structs == o["structs"]).all(), what
+                assert (od.Values == o["values"]).all(), f"{what}: {int((od.Values != o['values']).sum())} value bytes differ"
+                assert st.global_scale == np.float32(o["scale"]), what
+                assert tuple(st.global_offset) == tuple(np.float32(c) for c in o["offset"]), what
+            # not vacuous: which of the tied points wins decides the bytes
+            a, b = tie_reference(oracle_mod, cloud, order, False, depth)[1], tie_reference(oracle_mod, cloud, order, True, depth)[1]
+            assert (a["structs"] == b["structs"]).all() and (a["values"] != b["values"]).mean() > 0.5, f"{cloud} depth {depth} {order}"
+
+
 @pytest.mark.gpu
 def test_builder_gives_its_pool_back(sb):
     # the builder keeps its work arrays' device memory for the next build; sdfhip_sdfgen_trim returns it, and the next build is the same
@@ -235,7 +298,7 @@ def test_points_to_scene_without_leaving_the_device(sb):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("flavour", ["product", "lab"])
-def test_builder_scene_agrees_with_the_uploaded_tree_on_edge_clouds(flavour):
+def test_builder_scene_agrees_with_the_uploaded_tree_on_edge_clouds(flavour, oracle_mod):
     # sdfhip_sdfgen_scene hands its own tree to the scene without validating it again (the product; the laboratory
     # library validates it and refuses a verdict that differs from the builder's word).  On the clouds where a builder could
     # stop early or build a single node, the scene it makes must be the scene an upload of the same tree makes: depth, kernel
@@ -247,11 +310,18 @@ def test_builder_scene_agrees_with_the_uploaded_tree_on_edge_clouds(flavour):
     else:
         import sdfbox_amd as sb
     one = np.array([[0.1, 0.2, 0.3, 0.0, 0.0, 1.0]], np.float32)
+    opposite = np.repeat(one, 2, 0)
+    opposite[1, 3:] *= -1                                   # an exact tie whose winner decides the signs: the first point must win
     cases = {"one point": (one, 3), "two coincident points": (np.repeat(one, 2, 0), 4),
+             "two coincident points, opposite normals": (opposite, 4), "two coincident points, opposite normals, the other first": (opposite[::-1].copy(), 4),
              "eight points, depth 10": (fib_sphere(8), 10), "depth 0: the root alone": (fib_sphere(500), 0),
              "depth 1": (fib_sphere(500), 1), "a flat cloud (one plane)": (np.concatenate([fib_sphere(300)[:, :2], np.zeros((300, 1), np.float32),
                                                                            np.tile(np.float32([0, 0, 1]), (300, 1))], 1), 6)}
     for name, (v, depth) in cases.items():
+        if "coincident" in name:                            # ... and these trees are the oracle's, byte for byte
+            o = oracle_mod.sdfgen(v, depth)
+            od = sb.OctData.SdfGen(v, depth)
+            assert (od.Structs == o["structs"]).all() and (od.Values == o["values"]).all(), name
         try:
             od = sb.OctData.SdfGen(v, depth)
         except sb.SdfHipError:

@@ -87,6 +87,26 @@ def test_bands_dealt_by_cost():
     assert len(band_costs(torch.zeros(1080, 1920), 16)) == 68 and len(band_costs(torch.zeros(37, 50), 16)) == 3
 
 
+def test_eight_ranks_and_fewer_bands_than_ranks():
+    # a frame with fewer bands than ranks: round robin and the credit deal leave the ranks behind the bands without one (their
+    # shares are padding, and no row comes from them); a deal by cost cannot give every rank a band, and says so
+    from sdfbox_amd.tiles import BandLayout, balanced_owner
+    for w0 in (1.0, 0.6):
+        lay = BandLayout(37, 8, 16, w0)
+        n = [len(lay.bands_of(r)) for r in range(8)]
+        assert lay.n_bands == 3 and sum(n) == 3 and max(n) == 1 and lay.rows_per_rank == 16, (w0, n)
+        assert {lay.source_of(y)[0] for y in range(37)} == {r for r in range(8) if n[r]}
+        assert [lay.source_of(y) for y in (0, 15, 16, 31, 32, 36)] == [(lay.owner[0], 0), (lay.owner[0], 15), (lay.owner[1], 0),
+                                                                       (lay.owner[1], 15), (lay.owner[2], 0), (lay.owner[2], 4)]
+    assert BandLayout(37, 8, 16).owner == [0, 1, 2]
+    with pytest.raises(ValueError):
+        balanced_owner([5.0, 1.0, 1.0], 8)
+    with pytest.raises(ValueError):
+        BandLayout(37, 8, 16, owner=[0, 1, 2])
+    own = balanced_owner([3.0, 1.0, 4.0, 1.0, 5.0, 9.0, 2.0, 6.0], 8, extra0=2.0)         # as many bands as ranks: one each
+    assert sorted(own) == list(range(8)) and BandLayout(61, 8, 8, owner=own).rows_per_rank == 8
+
+
 def wire_pack(img):
     """numpy model of the kernel's wire buffer (FrameSink mode 3, raymarch_kernels.h): every pixel is
     (a, a, a, n), n <= 140, or the sky constant (0.005, 0.01, 0.2, n), n <= 100 -> a plane of floats
@@ -193,7 +213,11 @@ def _rank_main(rank, world, port, W, H, band_rows, q, rank0_weight=1.0, wire=Fal
 
 @pytest.mark.parametrize("world,H,band_rows,rank0_weight,wire", [(2, 40, 8, 1.0, False), (2, 37, 16, 1.0, False),
                                                                  (2, 56, 8, 0.6, True), (2, 56, 8, "cost", False),
-                                                                 (3, 61, 8, "cost", True)])
+                                                                 (3, 61, 8, "cost", True),
+                                                                 # cfg-4's eight ranks: three bands for eight ranks (five ranks send
+                                                                 # a share of padding only), the same dealt by credit with a lighter
+                                                                 # rank 0, and a deal by cost of 17 bands
+                                                                 (8, 37, 16, 1.0, False), (8, 37, 16, 0.6, True), (8, 130, 8, "cost", False)])
 def test_two_rank_gather_reassembles_the_frame(world, H, band_rows, rank0_weight, wire):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
