@@ -13,6 +13,7 @@ next ones.  Prints ONE JSON line on rank 0.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # N > 1 without a launcher: spawns that command itself (see spawn_ranks)
+    python bench.py --full ...            # + everything the line can carry besides its headline (see --full)
 """
 import argparse
 import hashlib
@@ -66,12 +67,19 @@ def parse():
                     help="gloo: rehearse the N>1 path through host buffers (not a perf mode)")
     ap.add_argument("--exercise-gather", action="store_true",
                     help="run the sharded path (bands + gather + de-interleave) even with one rank")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="wall-time target of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need, after its timed region: the CPU baseline, the "
+                         "box's HBM bandwidth, the `auto` forms of --configs, --sustained and --live-pmc, a sharded run's steady state "
+                         "and its frames against a whole-frame render (N > 1), a --single-process run's latency passes.  Without it a run "
+                         "sets up, warms up, times its steps, dumps its frame and prints its line; what an explicit --configs / "
+                         "--sustained / --live-pmc / --check asks for runs either way.  (The passes before the warm-up -- the latency "
+                         "figures -- run either way: they are the frames that bring the GPU's clocks up before the timed region.)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="wall-time target of the cpu_baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--configs", default="auto", choices=["auto", "all", "none"],
                     help="the other single-GPU BASELINE configurations timed in the same process, behind the headline: cfg-3 (4K, "
                          "compaction off and on), cfg-5 (4K, 16 spp), cfg-2 on the depth-10 scene -> the line's `configs` block.  "
-                         "auto: when the command is the headline's (1 GPU, 1920x1080, default scene and kernel); all: always; none")
+                         "auto: with --full when the command is the headline's (1 GPU, 1920x1080, default scene and kernel); all: always; none")
     ap.add_argument("--configs-scale", type=int, default=1,
                     help="tests only: the `configs` block on frames 1/N the size and the deeper scene at --depth + 1 (no PMC pass matches)")
     ap.add_argument("--display", action="store_true",
@@ -94,7 +102,7 @@ def parse():
     ap.add_argument("--one-kernel", action="store_true",
                     help="A/B: round 1's one-kernel form (lane state machine, shading in place) instead of the default "
                          "k_march (wave-converged march / shading / shadow march)")
-    ap.add_argument("--check", action="store_true", help="verify the assembled frame against a whole-frame render (always done when several ranks take part)")
+    ap.add_argument("--check", action="store_true", help="verify the assembled frame against a whole-frame render (with --full, always done when several ranks take part)")
     ap.add_argument("--rank0-weight", type=float, default=0.0,
                     help="sharded runs: rank 0's share of the frame as a fraction of a peer's share "
                          "(0 = measure at start-up so that render + assembly on rank 0 takes as long as a peer's render)")
@@ -131,14 +139,14 @@ def parse():
                     help="continuous-operation legs behind the headline (bench_sustained.py): 'cfg2,cfg3,orbit' seconds of wall time, e.g. "
                          "'5,3,2' -- the cfg-2 frame pipelined for >= 5 s, the 4K frame (in the `configs` block) for >= 3 s, the cfg-2 frame "
                          "with a camera that moves every frame for >= 2 s, the GPU's clock / power / temperature sampled every 100 ms.  "
-                         "auto: 5,3,2 when the command is the headline's, else off; 0 or off: none")
+                         "auto: 5,3,2 with --full when the command is the headline's, else off; 0 or off: none")
     ap.add_argument("--live-pmc", default="auto", choices=["auto", "on", "all", "off"],
                     help="the roofline's counters measured in this run (bench_live_pmc.py): after the timed region, the headline's command is run "
                          "again as child processes under `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE, the VALU counters: one pass each, 5 frames) and "
                          "`roofline.traffic` comes from those passes, the committed figure beside it.  on: the headline's command only (about 8 s "
-                         "more); auto / all: when the command is the headline's and rocprofv3 is there, also the moving-camera pass and every entry "
-                         "of the `configs` block, each through child passes of its own command line (about a minute more); off: the committed "
-                         "passes only (--only-timed implies off)")
+                         "more); all: when the command is the headline's and rocprofv3 is there, also the moving-camera pass and every entry "
+                         "of the `configs` block, each through child passes of its own command line (about a minute more); auto: all with "
+                         "--full, else off; off: the committed passes only (--only-timed implies off)")
     ap.add_argument("--lab", action="store_true",
                     help="load the experiments flavour of the library (libsdfhip_lab.so, include/sdfhip_experimental.h): needed by the A/B "
                          "forms --one-kernel and --shadow-queue")
@@ -196,7 +204,7 @@ def main():
     if args.single_process or args.devices:
         if "WORLD_SIZE" in os.environ and world > 1:
             raise SystemExit("--single-process is one process for all devices: start it without a launcher")
-        return main_single_process(args, json_fd)
+        return main_single_process(args, json_fd, full=args.full)
     if world != args.gpus:
         if "WORLD_SIZE" not in os.environ and args.gpus > 1:
             os.dup2(json_fd, 1)
@@ -747,7 +755,7 @@ def main():
     # ... and the run's STEADY STATE beside a short run's burst: a short sharded run (tiles.is_burst) deals its bands as that
     # burst and launches in tile order; the same deal rendered for >= 16 fills of the pipeline in the default order is what a long run gets
     steady = None
-    if sharded and world > 1 and pt is None and args.orbit == 0:
+    if args.full and sharded and world > 1 and pt is None and args.orbit == 0:
         n_steady = max(args.steps, 16 * G * nbuf)
         saved_flags = flags
         if plan_ordered and not args.tile_order:
@@ -762,8 +770,9 @@ def main():
 
     wd.phase("check (assembled frames against a whole-frame render)")
     check_ok = None
-    # (always when several ranks took part: a scaling curve is worth what its frames are -- one whole-frame render and a few compares)
-    if (args.check or world > 1) and sharded and rank == 0:
+    # (with --full, always when several ranks took part: a scaling curve is worth what its frames are -- one whole-frame render and a
+    # few compares)
+    if (args.check or (args.full and world > 1)) and sharded and rank == 0:
         refs = {}
 
         def ref_of(k):                     # the whole-frame render of frame k's camera
@@ -790,7 +799,7 @@ def main():
     wd.phase("report (bandwidth, configs, cpu baseline: rank 0 alone, no collective)", quiet=world == 1)
     if rank == 0:
         sec_per_step = elapsed / args.steps
-        copy_gbs = measured_hbm_bandwidth(sb, device)   # the box's own figure beside the nameplate
+        copy_gbs = measured_hbm_bandwidth(sb, device) if args.full else None   # the box's own figure beside the nameplate
         mode = "spp%d" % args.spp if pt is not None else "display" if args.display else "compact" if compact else "default"
         if args.shadow_queue and not compact and pt is None and not args.one_kernel:
             mode += ":shadow-queue"
@@ -822,7 +831,7 @@ def main():
             if "did not end within" in str(r.get("dropped", "")):
                 live_state["broken"] = "an earlier pass of this run hung (" + r["dropped"] + ")"
             return r
-        if headline and args.live_pmc != "off" and not args.only_timed and not args.lab:
+        if headline and args.live_pmc != "off" and (args.full or args.live_pmc != "auto") and not args.only_timed and not args.lab:
             wd.phase("live PMC passes (this command again, as children under rocprofv3 --pmc)", quiet=True)
             torch.cuda.synchronize()
             pmc, live_note = merge_pmc(live([], frames_per_launch), pmc)
@@ -847,7 +856,7 @@ def main():
             if isinstance(roof.get("traffic_source"), dict):
                 roof["traffic_source"]["live"] = live_note.get("used") == "live"
         # ---- continuous operation: the same frames, pipelined the same way, for seconds; clocks sampled ----
-        sus_s = sustained_seconds(args.sustained, headline)
+        sus_s = sustained_seconds(args.sustained, headline and args.full)
         sustained = telemetry = None
         if any(sus_s) and world == 1 and not sharded and pt is None:
             wd.phase("sustained legs (continuous rendering, clock / power / temperature sampled every 100 ms)", quiet=True)
@@ -976,7 +985,7 @@ def main():
             out["config"]["assembled_frame_equals_whole_frame_render"] = check_ok
         if sustained is not None:
             out["sustained"] = sustained
-        if args.configs == "all" or (args.configs == "auto" and headline):
+        if args.configs == "all" or (args.configs == "auto" and headline and args.full):
             # (the headline's buffers are not needed any more: the path-traced configuration wants 30 GB of queues)
             local = send = frame = gathered = None
             torch.cuda.empty_cache()
@@ -987,7 +996,7 @@ def main():
                                              live=live if live_all else None)
             except Exception as e:
                 out["configs"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(od, cam, W, H, args.cpu_seconds)
             except Exception as e:

@@ -60,11 +60,12 @@ class Watchdog:
                       file=sys.stderr, flush=True)
 
 
-def main_single_process(args, json_fd):
+def main_single_process(args, json_fd, full=True):
     """`--single-process`: the N-device frame behind the library's one call (sdfhip_multi_submit / _wait): one process, one
     host thread and one stream per device inside libsdfhip.so, sparse shares written by the march kernel, pushed into
     device 0 over the peers' own links, assembled there.  Same workload, same JSON line; `config.parallelism` says which
-    of the two things it measures."""
+    of the two things it measures.  full (bench.py --full): also the latency, host-frame and bandwidth passes behind the
+    timed region."""
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")           # (see main())
     import torch
@@ -142,23 +143,25 @@ def main_single_process(args, json_fd):
 
     run(args.warmup if args.warmup > 0 else 1)
     elapsed = run(args.steps, collect=True)
-    # one frame alone across the devices: submit + wait, nothing else in flight (median)
-    lat = []
-    for j in range(20 if pt is None else 3):
-        sync_all()
-        t = time.perf_counter()
-        ms.Submit(0, cams[j % len(cams)], W, H, flags=flags, pt=pt)
-        ms.Wait(0)
-        lat.append(time.perf_counter() - t)
-    latency_ms = float(np.median(lat)) * 1e3
-    # the frame to a HOST array, one call (what the C# host makes): sdfhip_multi_render
     host = np.empty((H, W, 4), dtype=np.uint8 if args.display else np.float32)
-    hl = []
-    for j in range(8 if pt is None else 2):
-        t = time.perf_counter()
-        ms.Draw(cams[j % len(cams)], W, H, flags=flags, pt=pt, out=host)
-        hl.append(time.perf_counter() - t)
-    host_ms = float(np.median(hl[1:])) * 1e3
+    latency_ms = host_ms = None
+    if full:
+        # one frame alone across the devices: submit + wait, nothing else in flight (median)
+        lat = []
+        for j in range(20 if pt is None else 3):
+            sync_all()
+            t = time.perf_counter()
+            ms.Submit(0, cams[j % len(cams)], W, H, flags=flags, pt=pt)
+            ms.Wait(0)
+            lat.append(time.perf_counter() - t)
+        latency_ms = round(float(np.median(lat)) * 1e3, 4)
+        # the frame to a HOST array, one call (what the C# host makes): sdfhip_multi_render
+        hl = []
+        for j in range(8 if pt is None else 2):
+            t = time.perf_counter()
+            ms.Draw(cams[j % len(cams)], W, H, flags=flags, pt=pt, out=host)
+            hl.append(time.perf_counter() - t)
+        host_ms = round(float(np.median(hl[1:])) * 1e3, 4)
 
     check_ok = None
     one = sb.Scene(od, device=devices[0])
@@ -185,7 +188,7 @@ def main_single_process(args, json_fd):
     px_bytes = 4 if args.display else 16
     ref_bytes = 8 * st.n_nodes + 8 * st.n_samples + px_bytes * W * H
     own_bytes = 16 * st.n_loads + px_bytes * W * H
-    roof = roofline(sec_per_step, own_bytes, ref_bytes, None, measured_hbm_bandwidth(sb, devices[0]))
+    roof = roofline(sec_per_step, own_bytes, ref_bytes, None, measured_hbm_bandwidth(sb, devices[0]) if full else None)
     roof.update({"time_ms": round(sec_per_step * 1e3, 4), "note": "no PMC pass exists for a multi-device run: no fraction, only the demand figures"})
     n_st = max(1, len(stats_seen))
     out = {
@@ -195,7 +198,7 @@ def main_single_process(args, json_fd):
         "n_gpus": len(devices),
         "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(sec_per_step * 1e3, 4),
-        "latency_ms": round(latency_ms, 4),
+        "latency_ms": latency_ms,
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -215,11 +218,11 @@ def main_single_process(args, json_fd):
             "gathered_bytes_per_frame": round(sum(s.gathered_bytes for s in stats_seen) / n_st / G, 1),
             "float_tails_sent_again": int(sum(s.resends for s in stats_seen)),
             "rank_ms_per_group": [round(sum(s.rank_ms[r] for s in stats_seen) / n_st, 4) for r in range(len(devices))],
-            "host_frame_ms": round(host_ms, 4),
+            "host_frame_ms": host_ms,
             "output": "RGBA8, display pass at assembly" if args.display else "RGBA32F, alpha = step count",
             "scene_build_s": round(t_gen, 2),
         },
-        "latency": {"frames": 1, "ms": round(latency_ms, 4), "to_host_array_ms": round(host_ms, 4)},
+        "latency": {"frames": 1, "ms": latency_ms, "to_host_array_ms": host_ms},
         "roofline": roof,
     }
     if check_ok is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The round's bench lines (GPU box, via gpurun): gpurun_out/bench_lines/<tag>_<name>.json -> copy to profiles/bench_lines/
 R=${1:-r05}; O=gpurun_out/bench_lines; mkdir -p $O
-run() { n=$1; shift; python bench.py "$@" > $O/${R}_$n.json 2> $O/${R}_$n.err || echo "$n failed"; }
+run() { n=$1; shift; python bench.py --full "$@" > $O/${R}_$n.json 2> $O/${R}_$n.err || echo "$n failed"; }
 run driver_line_with_configs --steps 20 --warmup 5
 run 1080p_default
 run 1080p_one_frame_in_flight --no-cpu-baseline --frames-in-flight 1

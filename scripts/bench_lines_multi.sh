@@ -1,5 +1,5 @@
 R=r04; O=gpurun_out/bench_lines; mkdir -p $O
-run() { n=$1; shift; python bench.py "$@" > $O/${R}_$n.json 2> $O/${R}_$n.err || echo "$n failed"; }
+run() { n=$1; shift; python bench.py --full "$@" > $O/${R}_$n.json 2> $O/${R}_$n.err || echo "$n failed"; }
 run sharded_1rank_nccl_4k --no-cpu-baseline --exercise-gather --check --size 3840x2160
 run sharded_2rank_gloo_1080p --no-cpu-baseline --gpus 2 --backend gloo --check --steps 40 --warmup 8
 run multi_4k_groups_1rank --single-process --devices 0 --size 3840x2160 --check --steps 64 --warmup 16

@@ -2,7 +2,7 @@
 # Round 6's bench lines (GPU box, via gpurun): gpurun_out/bench_lines/r06_<name>.json -> copy to profiles/bench_lines/
 # Run AFTER scripts/summarise_all.py r06 + compulsory_bytes.py r06 --install of the same build, so that the lines find their counters.
 R=${1:-r06}; O=gpurun_out/bench_lines; mkdir -p $O
-run() { n=$1; shift; python bench.py "$@" > $O/${R}_$n.json 2> $O/${R}_$n.err || echo "$n failed"; }
+run() { n=$1; shift; python bench.py --full "$@" > $O/${R}_$n.json 2> $O/${R}_$n.err || echo "$n failed"; }
 run driver_line_with_configs --steps 20 --warmup 5
 run 1080p_default --no-cpu-baseline --configs none
 run 1080p_orbit --no-cpu-baseline --configs none --orbit 90

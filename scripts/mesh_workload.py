@@ -20,7 +20,7 @@ for depth in (9, 10):
             "save_asdf_ms": round((t3 - t2) * 1e3, 1)}
     print(info, flush=True)
     for extra, tag in (([], ""), (["--size", "3840x2160"], "_4k")):
-        r = subprocess.run([sys.executable, "bench.py", "--asdf", asdf, "--no-cpu-baseline"] + extra, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--asdf", asdf, "--no-cpu-baseline"] + extra, capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if not line:
             print(r.stderr[-2000:]); raise SystemExit(1)

@@ -27,7 +27,7 @@ def run_bench(*args, timeout=360):
 
 @pytest.mark.gpu
 def test_bench_line_small_workload():
-    j = run_bench("--steps", 3, "--warmup", 1, "--depth", 6, "--size", "320x200", "--cpu-seconds", 0.5)
+    j = run_bench("--full", "--steps", 3, "--warmup", 1, "--depth", 6, "--size", "320x200", "--cpu-seconds", 0.5)
     for k in REQUIRED:
         assert k in j, k
     assert j["n_gpus"] == 1 and j["steps"] == 3 and j["unit"] == "Mray/s" and j["dtype"] == "f32"
@@ -45,6 +45,21 @@ def test_bench_line_small_workload():
     assert 1 <= c["cores"] <= c["limits"]["affinity_cpus"] and c["value"] == max(e["value"] for e in c["sweep"])
     assert [e["threads"] for e in c["sweep"]][0] == 1 and c["one_thread"]["value"] == c["sweep"][0]["value"]
     assert c["native_build_equals_portable_build"] in (True, None)
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_measures_only_its_headline():
+    # without --full the run does what its headline needs and no more: no CPU baseline, no bandwidth kernels, no `configs`,
+    # `sustained` or live counter passes -- on the headline's own command as well (the committed counters still price the line)
+    j = run_bench("--steps", 3, "--warmup", 1)
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["unit"] == "Mray/s" and j["dtype"] == "f32" and j["higher_is_better"] is True
+    for k in ("cpu_baseline", "configs", "sustained", "steady_state"):
+        assert k not in j, k
+    assert j["roofline"]["measured_hbm_gbs"] is None and "live_pmc" not in j["roofline"] and j["roofline"]["time_ms"] == j["ms_per_step"]
+    # a sharded run checks its frames only when asked to
+    j = run_bench("--gpus", 2, "--backend", "gloo", "--steps", 8, "--warmup", 4, "--depth", 6, "--size", "640x360")
+    assert j["n_gpus"] == 2 and "assembled_frame_equals_whole_frame_render" not in j["config"] and "steady_state" not in j
 
 
 @pytest.mark.gpu
@@ -493,7 +508,7 @@ def test_run_group_ends_the_whole_group_at_its_timeout(tmp_path):
 def test_headline_counts_its_own_bytes_through_child_passes():
     # the headline's command with everything behind the timed region switched off but the live counter passes: roofline.traffic comes
     # from rocprofv3 --pmc children of this very run and agrees with the committed pass of the same build
-    j = run_bench("--steps", 5, "--warmup", 1, "--no-cpu-baseline", "--configs", "none", "--sustained", "off")
+    j = run_bench("--full", "--steps", 5, "--warmup", 1, "--no-cpu-baseline", "--configs", "none", "--sustained", "off")
     r = j["roofline"]
     lp = r["live_pmc"]
     if lp["used"] != "live":                                  # a box without a usable rocprofv3: the committed figure, and the reason
