@@ -7,7 +7,9 @@
 //   possible    = candidates within (centerValue + sqrt(3)/2 * scale)       k_center_* (count),
 //                 of the centre, in list order                              k_corners_* (stable compaction)
 //   corner i    = signed distance to the nearest *surviving* point, unless  k_corners_*
-//                 inherited from the parent (child i inherits corner i)
+//                 inherited from the parent (child i inherits corner i; an
+//                 inherited +inf is recomputed, as every corner still at
+//                 INFINITY is, dllmain.cpp:171-172)
 //   split       = centerValue < 2 * scale && depth < MaxDepth               k_corners_*
 // (levels of fewer than 16 384 nodes: k_center_seg_min / _seg_count, k_corners_seg / _fin -- several workgroups per node;
 //  the others: k_center_sib / k_corners_sib -- a wavefront per sibling block, the shared list staged through LDS)
@@ -351,8 +353,8 @@ __global__ __launch_bounds__(256) void k_corners_fin(GenParams P, LevelArrays L,
     const Best b = unpack_best(A.corner[8 * (size_t)node + i]);
     const uint32_t off = L.cand_off[node];
     float val;
-    if (i == L.slot[node]) {
-        val = L.inherit[node];                           // n[i] = vals[insert][i], dllmain.cpp:181
+    if (i == L.slot[node] && L.inherit[node] != INFINITY) {
+        val = L.inherit[node];                           // n[i] = vals[insert][i], dllmain.cpp:181 -- kept unless +inf (:171-172)
     } else if (no_centre || b.k == 0xFFFFFFFFu || isinf(b.d) || isnan(b.d)) {
         atomicExch(err, 2u);
         val = 0.0f;
@@ -591,8 +593,8 @@ __global__ __launch_bounds__(64) void k_corners_sib(GenParams P, LevelArrays L, 
     float q0, q1, q2;
     transform(P, px + (float)(i % 2) * P.scale, py + (float)((i / 2) % 2) * P.scale, pz + (float)((i / 2 / 2) % 2) * P.scale, q0, q1, q2);
     float val;
-    if (i == slot) {
-        val = L.inherit[node];                           // n[i] = vals[insert][i], dllmain.cpp:181
+    if (i == slot && L.inherit[node] != INFINITY) {
+        val = L.inherit[node];                           // n[i] = vals[insert][i], dllmain.cpp:181 -- kept unless +inf (:171-172)
     } else if (b.k == 0xFFFFFFFFu || isinf(b.d) || isnan(b.d)) {
         atomicExch(err, 2u);
         val = 0.0f;
