@@ -178,6 +178,18 @@ public:
         if (scene) sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Space carving (sdfhip_scene_edit; the reference's README lists modeling under "Plans"): the brushes, in order, carve from or
+    // add to the loaded model on its device, and the edited model replaces it as a reload does -- the old handle is freed once the
+    // new one exists.  max_depth: -1 = the model's depth, else 0..12.  host_out (may be null): the edited tree's host arrays
+    // (release with sdfhip_octdata_free), e.g. for sdfhip_asdf_save
+    void Edit(const std::vector<sdfhip_edit> &edits, int max_depth = -1, sdfhip_edit_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Edit: no model loaded");
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_edit(scene, edits.data(), (uint32_t)edits.size(), max_depth, &fresh, host_out, stats));
+        sdfhip_scene_free(scene);
+        scene = fresh;
+    }
     // Draw's UpdateBuffer(info) + DispatchSized(W, H, 1), Program.cs:81,94 -> RGBA32F frame
     void Draw(const Info &state, int width, int height, std::vector<float> &frame, uint32_t flags = 0)
     {

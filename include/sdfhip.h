@@ -452,6 +452,45 @@ SDFHIP_API int sdfhip_deinterleave_sparse2_device(int device, const void *const 
                                                   const uint8_t *owner, uint32_t capacity, uint32_t frames, uint32_t flags,
                                                   int only_rank, uint32_t *counts_out, void *stream);
 
+/* ---- space carving: brush edits of a resident scene -----------------------------------------------
+ * Replaces: nothing in the reference's code -- its README lists "Add support for modeling, as efficient space carving is one of
+ * the main benefits of distance fields" under "Plans", and a tree there is immutable once built.
+ * sdfhip_scene_edit applies n_edits brushes, in order, to the tree of `scene` on its device and returns the result as a NEW handle
+ * `*out` on the same device: the input is untouched (frames in flight on it included) and either handle may be freed first.  A list
+ * gives byte for byte the tree that chained single calls give; n_edits = 0 is a clone.  The arithmetic is pinned (fp32, in the
+ * order written):
+ *   brush s(p): sphere sqrtf((dx*dx + dy*dy) + dz*dz) - r; box q = |p - c| - h, sqrtf(|max(q, 0)|^2) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0);
+ *               g = -s to carve (subtract), g = s to add (union)
+ *   bytes:      q(f, S) = floorf(saturate(f/2/S + 0.25f) * 255) (SdfGen's FromFloat); a corner's byte becomes max(p, q(g, S))
+ *               (carve) or min(p, q(g, S)) (add), p its byte before the edit
+ *   refinement: a leaf above max_depth whose centre has |s| < 2 S (the builder's band, Model.cs:44) and where the brush wins over
+ *               the trilinear value of its corners (carve: g > v, add: g < v) gets 8 children, whose values before the edit are
+ *               the parent's, interpolated; they are edited by the same rules, recursively.  Nothing is pruned.
+ *   node order: original nodes keep their indices; new blocks of 8 are appended in the order (depth of the block, parent index).
+ * max_depth: -1 = the input's depth, else 0..12 (deeper than the input lets brushes refine past it).  host_out (may be NULL): the
+ * result's host arrays, as sdfhip_sdfgen_scene's `out` (release with sdfhip_octdata_free).  stats (may be NULL).
+ * SDFHIP_ERR_ARG: a null pointer, an unknown op or brush, a non-finite parameter, r <= 0 or h <= 0, max_depth outside -1..12, a
+ * result of more than 2^31 - 1 nodes; SDFHIP_ERR_BAD_TREE: the input is not consistent (stack_kernel_ok == 0 in
+ * sdfhip_scene_info); SDFHIP_ERR_NOMEM: out of device memory (the input stays valid, nothing leaks).
+ * Work is proportional to the nodes near and inside the brushes, not to the tree; the new handle builds its lookup grids anew. */
+enum { SDFHIP_EDIT_CARVE = 0, SDFHIP_EDIT_ADD = 1 };          /* subtract / union */
+enum { SDFHIP_BRUSH_SPHERE = 0, SDFHIP_BRUSH_BOX = 1 };
+typedef struct sdfhip_edit {
+    int32_t op, brush;
+    float params[6];        /* sphere: cx cy cz r; box: cx cy cz hx hy hz (axis-aligned, half extents) */
+} sdfhip_edit;
+typedef struct sdfhip_edit_stats {
+    uint32_t nodes_in, nodes_out;
+    uint32_t nodes_visited;  /* nodes whose bytes the edits evaluated: original nodes the brushes reach, and every new node */
+    uint32_t nodes_changed;  /* original nodes whose bytes changed (a node edited by several brushes counts once per brush) */
+    uint32_t blocks_added, depth_out;
+    float edit_ms;           /* HIP events around the edit's kernels */
+    float scene_ms;          /* building the new handle (fused records, lookup grids), host clock */
+    float total_ms;          /* host clock, the whole call */
+} sdfhip_edit_stats;
+SDFHIP_API int sdfhip_scene_edit(sdfhip_scene *scene, const sdfhip_edit *edits, uint32_t n_edits, int32_t max_depth, sdfhip_scene **out,
+                                 sdfhip_octdata *host_out, sdfhip_edit_stats *stats);
+
 /* ---- one frame over several GPUs, behind one call -----------------------------------------------------------
  * Replaces: Program.Draw's UpdateBuffer(info) + DispatchSized(W, H, 1) (SdfBox/Program.cs:81,94) when the frame is rendered by
  * the GPUs of a node: the host still makes ONE call per frame.  One process; the scene is replicated on every device at

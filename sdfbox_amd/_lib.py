@@ -42,12 +42,14 @@ TUNE_SHADOW_QUEUE = 0x80000   # FLAG_COMPACT's kernels with EVERY shadow ray que
 TUNE_PERSISTENT_WAVES = 0x400000   # with FLAG_COMPACT on a grid scene: the persistent-wave lane-refill kernel (k_compact), the flag's form until round 4
 TUNE_BYTE_CELLS = 0x200000    # on a scene uploaded under SDFHIP_SAMPLE_RECORDS=1: back to the 16-byte cells every other scene reads
 SHAPE_SPHERE, SHAPE_TORUS, SHAPE_GYROID = 0, 1, 2
+EDIT_CARVE, EDIT_ADD = 0, 1          # sdfhip_scene_edit: subtract / union
+BRUSH_SPHERE, BRUSH_BOX = 0, 1
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import COctData, CPoints, Info, MultiLink, MultiStats, PathTrace, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import COctData, CPoints, Edit, EditStats, Info, MultiLink, MultiStats, PathTrace, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -140,6 +142,21 @@ else:
         ]
 
 
+    class Edit(ctypes.Structure):
+        """sdfhip_edit: one brush.  params: sphere (cx, cy, cz, r); box (cx, cy, cz, hx, hy, hz), axis-aligned half extents."""
+        _fields_ = [("op", ctypes.c_int32), ("brush", ctypes.c_int32), ("params", ctypes.c_float * 6)]
+
+        def __init__(self, op, brush, params):
+            p = [float(x) for x in params] + [0.0] * (6 - len(params))
+            super().__init__(int(op), int(brush), (ctypes.c_float * 6)(*p[:6]))
+
+
+    class EditStats(ctypes.Structure):
+        _fields_ = [("nodes_in", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("nodes_visited", ctypes.c_uint32),
+                    ("nodes_changed", ctypes.c_uint32), ("blocks_added", ctypes.c_uint32), ("depth_out", ctypes.c_uint32),
+                    ("edit_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
     class SdfHipError(RuntimeError):
         def __init__(self, code, message):
             super().__init__(f"sdfhip error {code}: {message}")
@@ -202,6 +219,8 @@ _SIG = {
     "sdfhip_camera_update": (None, [_c.POINTER(Info), _c.POINTER(_c.c_float), _c.c_float, _c.c_uint32, _c.c_float]),
     "sdfhip_camera_mouse_move": (None, [_c.POINTER(Info), _c.POINTER(_c.c_float), _c.c_float, _c.c_float]),
     "sdfhip_camera_mouse_wheel": (_c.c_float, [_c.c_float, _c.c_float]),
+    "sdfhip_scene_edit": (_c.c_int, [_vp, _c.POINTER(Edit), _c.c_uint32, _c.c_int32, _c.POINTER(_vp), _c.POINTER(COctData),
+                                     _c.POINTER(EditStats)]),
     "sdfhip_scene_top_grid": (_c.c_int, [_vp, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_uint64)]),
     "sdfhip_render_bands_device": (_c.c_int, [_vp, _c.POINTER(Info), _c.c_uint32, _c.POINTER(PathTrace), _c.c_uint32,
                                               _c.c_uint32, _c.c_uint32, _c.POINTER(_c.c_uint16), _c.c_uint32,

@@ -27,6 +27,7 @@
 // nearest-point search go to the earliest list position, as the reference's strict `<`
 // scan does; `minDistance < 0.015` is a double comparison, as there.
 #include "abi_guard.h"
+#include "sdf_bytes.h"
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -772,9 +773,7 @@ __global__ void k_emit(const uint32_t *__restrict__ split, const int32_t *__rest
     uint32_t lo = 0, hi = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++) {                        // FromFloat, dllmain.cpp:192-196
-        const float normd = vals[8 * (size_t)c + k] / 2 / scale;
-        const float sat = fminf(fmaxf(normd + 0.25f, 0.0f), 1.0f);
-        const uint32_t b = (uint32_t)floorf(sat * 255);
+        const uint32_t b = from_float(vals[8 * (size_t)c + k], scale);
         if (k < 4) lo |= b << (8 * k); else hi |= b << (8 * (k - 4));
     }
     ((uint2 *)V)[idx] = make_uint2(lo, hi);

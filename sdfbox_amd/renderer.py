@@ -103,6 +103,29 @@ class Scene:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
 
+    def Edit(self, edits, max_depth=None, want_octdata=False, want_stats=False):
+        """Space carving (sdfhip_scene_edit): the brushes `edits` -- Edit objects, or (op, brush, params) tuples, applied in order --
+        carve from (EDIT_CARVE) or add to (EDIT_ADD) this scene's tree on its device; the result is a NEW Scene, this one is left as
+        it was.  max_depth: None = this tree's depth, else 0..12 (deeper lets the brushes refine past it).  want_octdata: also the
+        result's host arrays (e.g. for OctData.Save); want_stats: an EditStats."""
+        from .octdata import OctData
+        items = [e if isinstance(e, _lib.Edit) else _lib.Edit(*e) for e in edits]
+        arr = (_lib.Edit * max(1, len(items)))(*items)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = self.device
+        raw = _lib.COctData()
+        st = _lib.EditStats()
+        check(lib.sdfhip_scene_edit(self._h, arr, len(items), -1 if max_depth is None else int(max_depth), ctypes.byref(res._h),
+                                    ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
     def close(self):
         if self._h:
             lib.sdfhip_scene_free(self._h)
