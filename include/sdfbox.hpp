@@ -190,6 +190,31 @@ public:
         sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Point and ray queries (sdfhip_scene_sample / _raycast / _pick; nothing in the reference corresponds): what the loaded model
+    // answers without drawing a frame, with the shader's own arithmetic.  Sample: distance, cell and gradient at points (xyz: 3 floats
+    // per point); Raycast: the primary march of Compute.hlsl:194-203 for arbitrary rays; Pick: that march for pixels {x, y} of the
+    // camera `state` -- Pick one pixel, put a brush at hit.position, Edit.  A bad element gets SDFHIP_QUERY_INVALID, not an exception.
+    std::vector<sdfhip_probe> Sample(const std::vector<float> &xyz)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Sample: no model loaded");
+        std::vector<sdfhip_probe> out(xyz.size() / 3);
+        Check(sdfhip_scene_sample(scene, xyz.data(), (uint32_t)out.size(), out.data()));
+        return out;
+    }
+    std::vector<sdfhip_hit> Raycast(const std::vector<sdfhip_ray> &rays, float margin, float limit, uint32_t max_steps = 100)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Raycast: no model loaded");
+        std::vector<sdfhip_hit> out(rays.size());
+        Check(sdfhip_scene_raycast(scene, rays.data(), (uint32_t)rays.size(), margin, limit, max_steps, out.data()));
+        return out;
+    }
+    std::vector<sdfhip_hit> Pick(const Info &state, const std::vector<uint32_t> &pixels_xy, uint32_t max_steps = 100)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Pick: no model loaded");
+        std::vector<sdfhip_hit> out(pixels_xy.size() / 2);
+        Check(sdfhip_scene_pick(scene, &state, pixels_xy.data(), (uint32_t)out.size(), max_steps, out.data()));
+        return out;
+    }
     // Draw's UpdateBuffer(info) + DispatchSized(W, H, 1), Program.cs:81,94 -> RGBA32F frame
     void Draw(const Info &state, int width, int height, std::vector<float> &frame, uint32_t flags = 0)
     {

@@ -491,6 +491,68 @@ typedef struct sdfhip_edit_stats {
 SDFHIP_API int sdfhip_scene_edit(sdfhip_scene *scene, const sdfhip_edit *edits, uint32_t n_edits, int32_t max_depth, sdfhip_scene **out,
                                  sdfhip_octdata *host_out, sdfhip_edit_stats *stats);
 
+/* ---- point and ray queries: what a resident scene answers without drawing a frame -------------------
+ * Replaces: nothing in the reference's code -- its only consumer of the tree is Compute.hlsl; a host that wants the distance at a
+ * point (collision, placement, snapping) or the surface point under the cursor (where to put a brush) has no call to make there.
+ * Three questions, answered for a batch on the scene's device with the shader's own arithmetic (fp32, each operation rounded in the
+ * order written, fused where the oracle fuses: DESIGN.md section 3), so an answer is bit for bit what a pixel of a frame would
+ * have seen:
+ *   sample    per point: interpol_world(find(p)) from the root (Compute.hlsl:54-58, 88-108; oracle_distance_at), the cell find()
+ *             ended in, and gradient() (Compute.hlsl:112-130) in that cell at p
+ *   raycast   per ray: the primary march of Compute.hlsl:194-203 and where it ended
+ *   pick      per pixel of a camera block: the same march from info->position along the kernel's own ray() (Compute.hlsl:163-168)
+ *             for pixel (x, y) -- the shader's direction bit for bit, not a host re-computation -- with info's margin and limit:
+ *             "what is under the cursor"
+ * The march, pinned (oracle/sdf_oracle.c o_pixel's first loop; nothing added but t):
+ *     prox = 1; i = 0; t = 0; cursor at the root
+ *     while ((prox > margin * 2.0f || prox < 0.0f) && i < max_steps) {
+ *         if (dot(pos, pos) > limit) -> SDFHIP_QUERY_ESCAPED
+ *         find(pos); prox = interpol_world(pos); pos = fma(dir, prox, pos); t = t + prox; i++ }
+ *     -> SDFHIP_QUERY_HIT if !(prox > margin * 2.0f || prox < 0.0f), else SDFHIP_QUERY_EXHAUSTED
+ * A NaN prox (degenerate data) ends the loop exactly as it ends the shader's and is reported SDFHIP_QUERY_HIT with prox NaN.  A ray
+ * that starts inside the solid reads a negative prox and marches backwards, as the shader's rule has it.  The cursor is carried
+ * from step to step as in the shader (a position on a cell face belongs to the cell the cursor came from); sample starts every
+ * point at the root.  Points outside [0,1]^3 are answered the way find / interpol_world answer them (saturated), not refused.
+ * max_steps: 1..4096 (the shader's value is 100).  n = 0 is a success that touches nothing.
+ * SDFHIP_ERR_ARG: a null pointer, max_steps out of range, a non-finite margin or limit; SDFHIP_ERR_NOMEM / SDFHIP_ERR_DEVICE as
+ * elsewhere.  A bad ELEMENT is not an error of the call: it gets SDFHIP_QUERY_INVALID and zeros, and the rest of the batch is answered.
+ *   sdfhip_scene_sample / _raycast / _pick      host arrays, synchronous (staged through device memory on the scene's own stream)
+ *   sdfhip_scene_sample_device / _raycast_device  device pointers on the scene's device, asynchronous on `stream` (NULL = the HIP
+ *                                               default stream), no host synchronisation: sdfhip_render_device's convention
+ * xyz: n x 3 floats, packed.  pixels_xy: n x {x, y}.  Queries on one handle may run beside frames on other streams. */
+enum { SDFHIP_QUERY_HIT = 0,        /* the march ended by the shader's own test: !(prox > margin * 2 || prox < 0)
+                                       (sample: the point was looked up) */
+       SDFHIP_QUERY_ESCAPED = 1,    /* dot(pos, pos) > limit before a step (Compute.hlsl:195): the pixel would be sky */
+       SDFHIP_QUERY_EXHAUSTED = 2,  /* max_steps steps taken and the test still asks for more (the shader shades such a pixel anyway) */
+       SDFHIP_QUERY_INVALID = 3 };  /* a non-finite coordinate, or a direction that is not finite or is all zero: nothing was looked up */
+typedef struct sdfhip_probe {       /* 32 bytes: the answer for one point */
+    float distance;                 /* interpol_world(find(p)) from the root */
+    uint32_t node;                  /* index of the cell find() ended in */
+    float scale;                    /* its edge length */
+    uint32_t status;                /* SDFHIP_QUERY_HIT or SDFHIP_QUERY_INVALID */
+    float gradient[3];              /* gradient() in that cell at p: differences of the decoded corner values across the cell, not
+                                       normalised (d distance / d world = 2 * gradient) */
+    uint32_t pad_;
+} sdfhip_probe;
+typedef struct sdfhip_ray { float origin[3], pad0_, dir[3], pad1_; } sdfhip_ray;   /* 32 bytes; dir is used as given */
+typedef struct sdfhip_hit {         /* 48 bytes: where one ray's march ended */
+    float position[3];              /* pos when the loop ended (after the last step) */
+    float t;                        /* the steps' distances summed in fp32 in march order: ((p1 + p2) + p3) ... */
+    float normal[3];                /* HIT / EXHAUSTED: gradient() in the cursor's cell at `position`, times 1 / sqrt(dot(g, g)) as the
+                                       shader normalises (Compute.hlsl:209; a flat cell's zero gradient gives NaN there too); else 0 */
+    float prox;                     /* the last distance read (1.0f if no step was taken) */
+    uint32_t status, steps, node;   /* steps == the i of Compute.hlsl:194; node = the cursor's cell */
+    float scale;
+} sdfhip_hit;
+SDFHIP_API int sdfhip_scene_sample(sdfhip_scene *scene, const float *xyz, uint32_t n, sdfhip_probe *out);
+SDFHIP_API int sdfhip_scene_sample_device(sdfhip_scene *scene, const float *d_xyz, uint32_t n, sdfhip_probe *d_out, void *stream);
+SDFHIP_API int sdfhip_scene_raycast(sdfhip_scene *scene, const sdfhip_ray *rays, uint32_t n, float margin, float limit, uint32_t max_steps,
+                                    sdfhip_hit *out);
+SDFHIP_API int sdfhip_scene_raycast_device(sdfhip_scene *scene, const sdfhip_ray *d_rays, uint32_t n, float margin, float limit,
+                                           uint32_t max_steps, sdfhip_hit *d_out, void *stream);
+SDFHIP_API int sdfhip_scene_pick(sdfhip_scene *scene, const sdfhip_info *info, const uint32_t *pixels_xy, uint32_t n, uint32_t max_steps,
+                                 sdfhip_hit *out);
+
 /* ---- one frame over several GPUs, behind one call -----------------------------------------------------------
  * Replaces: Program.Draw's UpdateBuffer(info) + DispatchSized(W, H, 1) (SdfBox/Program.cs:81,94) when the frame is rendered by
  * the GPUs of a node: the host still makes ONE call per frame.  One process; the scene is replicated on every device at

@@ -44,12 +44,13 @@ TUNE_BYTE_CELLS = 0x200000    # on a scene uploaded under SDFHIP_SAMPLE_RECORDS=
 SHAPE_SPHERE, SHAPE_TORUS, SHAPE_GYROID = 0, 1, 2
 EDIT_CARVE, EDIT_ADD = 0, 1          # sdfhip_scene_edit: subtract / union
 BRUSH_SPHERE, BRUSH_BOX = 0, 1
+QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdfhip_probe.status / sdfhip_hit.status
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import COctData, CPoints, Edit, EditStats, Info, MultiLink, MultiStats, PathTrace, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import COctData, CPoints, Edit, EditStats, Hit, Info, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -157,6 +158,26 @@ else:
                     ("edit_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
 
 
+    class Probe(ctypes.Structure):
+        """sdfhip_probe: the answer for one point of sdfhip_scene_sample."""
+        _fields_ = [("distance", ctypes.c_float), ("node", ctypes.c_uint32), ("scale", ctypes.c_float), ("status", ctypes.c_uint32),
+                    ("gradient", ctypes.c_float * 3), ("pad_", ctypes.c_uint32)]
+
+
+    class Ray(ctypes.Structure):
+        """sdfhip_ray: origin and direction (used as given) of one ray of sdfhip_scene_raycast."""
+        _fields_ = [("origin", ctypes.c_float * 3), ("pad0_", ctypes.c_float), ("dir", ctypes.c_float * 3), ("pad1_", ctypes.c_float)]
+
+
+    class Hit(ctypes.Structure):
+        """sdfhip_hit: where one ray's march ended (sdfhip_scene_raycast, sdfhip_scene_pick)."""
+        _fields_ = [("position", ctypes.c_float * 3), ("t", ctypes.c_float), ("normal", ctypes.c_float * 3), ("prox", ctypes.c_float),
+                    ("status", ctypes.c_uint32), ("steps", ctypes.c_uint32), ("node", ctypes.c_uint32), ("scale", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(Probe), ctypes.sizeof(Ray), ctypes.sizeof(Hit)) == (32, 32, 48)
+
+
     class SdfHipError(RuntimeError):
         def __init__(self, code, message):
             super().__init__(f"sdfhip error {code}: {message}")
@@ -221,6 +242,11 @@ _SIG = {
     "sdfhip_camera_mouse_wheel": (_c.c_float, [_c.c_float, _c.c_float]),
     "sdfhip_scene_edit": (_c.c_int, [_vp, _c.POINTER(Edit), _c.c_uint32, _c.c_int32, _c.POINTER(_vp), _c.POINTER(COctData),
                                      _c.POINTER(EditStats)]),
+    "sdfhip_scene_sample": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
+    "sdfhip_scene_sample_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp, _vp]),
+    "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),
+    "sdfhip_scene_raycast_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp, _vp]),
+    "sdfhip_scene_pick": (_c.c_int, [_vp, _c.POINTER(Info), _vp, _c.c_uint32, _c.c_uint32, _vp]),
     "sdfhip_scene_top_grid": (_c.c_int, [_vp, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_uint64)]),
     "sdfhip_render_bands_device": (_c.c_int, [_vp, _c.POINTER(Info), _c.c_uint32, _c.POINTER(PathTrace), _c.c_uint32,
                                               _c.c_uint32, _c.c_uint32, _c.POINTER(_c.c_uint16), _c.c_uint32,

@@ -52,6 +52,18 @@ class HostFrame:
             pass
 
 
+def _rays(origins, dirs):
+    """(n, 3) origins and directions -> n sdfhip_ray records"""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("Raycast: as many directions as origins")
+    rays = np.zeros(len(o), dtype=np.dtype(_lib.Ray))
+    rays["origin"] = o
+    rays["dir"] = d
+    return rays
+
+
 class Scene:
     """A scene resident in one GPU's HBM (replaces the `data` / `values`
     bindings of Program.cs:147-152)."""
@@ -125,6 +137,43 @@ class Scene:
         if want_stats:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
+
+    # -- point and ray queries (sdfhip_scene_sample / _raycast / _pick): answers without a frame ---------------------------------
+    def Sample(self, points):
+        """Distance, cell and gradient at points (n, 3) float32, with the shader's own arithmetic: a structured array of n records
+        (fields of sdfhip_probe: distance, node, scale, status, gradient).  A non-finite point gets QUERY_INVALID and zeros."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(p), dtype=np.dtype(_lib.Probe))
+        check(lib.sdfhip_scene_sample(self._h, p.ctypes.data, len(p), out.ctypes.data))
+        return out
+
+    def Raycast(self, origins, dirs, margin, limit, max_steps=100):
+        """The shader's primary march (Compute.hlsl:194-203) for n arbitrary rays -- origins, dirs (n, 3) float32, dirs used as given:
+        a structured array of n sdfhip_hit records (position, t, normal, prox, status, steps, node, scale)."""
+        rays = _rays(origins, dirs)
+        out = np.zeros(len(rays), dtype=np.dtype(_lib.Hit))
+        check(lib.sdfhip_scene_raycast(self._h, rays.ctypes.data, len(rays), float(margin), float(limit), int(max_steps), out.ctypes.data))
+        return out
+
+    def Pick(self, state, pixels, max_steps=100):
+        """What is under the pixels (n, 2) {x, y} of the camera `state` (a Logic or an Info): the march of Raycast from the camera's
+        position along the kernel's own ray() for each pixel, margin and limit the camera's."""
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1, 2)
+        out = np.zeros(len(px), dtype=np.dtype(_lib.Hit))
+        info = state if isinstance(state, Info) else state.State
+        check(lib.sdfhip_scene_pick(self._h, ctypes.byref(info), px.ctypes.data, len(px), int(max_steps), out.ctypes.data))
+        return out
+
+    def SampleDevice(self, xyz_ptr, n, out_ptr, stream=None):
+        """Sample for n points (n x 3 floats) in device memory at `xyz_ptr` into n sdfhip_probe records at `out_ptr`, asynchronously
+        on `stream` (a raw hipStream_t value or None), as DrawDevice."""
+        check(lib.sdfhip_scene_sample_device(self._h, ctypes.c_void_p(int(xyz_ptr)), int(n), ctypes.c_void_p(int(out_ptr)),
+                                             ctypes.c_void_p(int(stream)) if stream else None))
+
+    def RaycastDevice(self, rays_ptr, n, margin, limit, out_ptr, max_steps=100, stream=None):
+        """Raycast for n sdfhip_ray records in device memory into n sdfhip_hit records at `out_ptr`, asynchronously on `stream`."""
+        check(lib.sdfhip_scene_raycast_device(self._h, ctypes.c_void_p(int(rays_ptr)), int(n), float(margin), float(limit), int(max_steps),
+                                              ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(stream)) if stream else None))
 
     def close(self):
         if self._h:
