@@ -13,7 +13,7 @@
 // One host synchronisation per level that has work, per edit: the counts of the next level size its launches and buffers.
 // Then the arrays go to scene_from_arrays (grids, fused records) as the point-cloud builder's do.
 #include "edit_kernels.h"
-#include "scene.h"
+#include "host_support.h"
 #include "abi_guard.h"
 
 #include <algorithm>
@@ -218,18 +218,13 @@ try {
     if (rc != SDFHIP_OK) return rc;
     const float scene_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (host_out) {
-        int32_t *hS = static_cast<int32_t *>(malloc(n_cur * 8));
-        uint8_t *hV = static_cast<uint8_t *>(malloc(n_cur * 8));
-        hipError_t e = (hS && hV) ? hipMemcpy(hS, dS, n_cur * 8, hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipMemcpy(hV, dV, n_cur * 8, hipMemcpyDeviceToHost);
+        bool no_host_memory = false;
+        const hipError_t e = tree_to_host(dS, dV, n_cur, malloc, host_out, &no_host_memory);
         if (e != hipSuccess) {
-            (void)hipGetLastError();
-            free(hS); free(hV);
             (void)sdfhip_scene_free(res);
-            return e == hipErrorOutOfMemory && !(hS && hV) ? fail(SDFHIP_ERR_NOMEM, "scene_edit: out of host memory for host_out")
-                                                           : fail(SDFHIP_ERR_DEVICE, "scene_edit: copying the tree to the host failed: %s", hipGetErrorString(e));
+            return no_host_memory ? fail(SDFHIP_ERR_NOMEM, "scene_edit: out of host memory for host_out")
+                                  : fail(SDFHIP_ERR_DEVICE, "scene_edit: copying the tree to the host failed: %s", hipGetErrorString(e));
         }
-        host_out->length = (uint32_t)n_cur; host_out->structs = hS; host_out->values = hV;
     }
     if (stats) {
         stats->nodes_in = scene->n; stats->nodes_out = (uint32_t)n_cur;

@@ -1,0 +1,70 @@
+// What the host side of libsdfhip.so shares beyond the scene handle.  Not one of the renderer's measured sources (bench_report.py
+// hashes scene.h, which this header includes and which must never include it): a helper a new translation unit needs goes here.
+#pragma once
+#include "scene.h"
+
+#include <thread>
+
+// HIP_TRY (scene.h) with a translation unit's prefix in front of the message.  Used through one-line aliases that pass #expr as
+// `text`, so that the message shows the call as it was written: #define M_TRY(expr) HIP_TRY_AS("multi: ", expr, #expr)
+#define HIP_TRY_AS(prefix, expr, text)                                                      \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            (void)hipGetLastError();   /* the runtime's record of it: a later launch check must not report it as its own */ \
+            return sdfhip::fail(SDFHIP_ERR_DEVICE, prefix "%s failed: %s", text, hipGetErrorString(e_)); \
+        }                                                                                   \
+    } while (0)
+
+namespace sdfhip {
+
+#if defined(__x86_64__) || defined(__i386__)
+inline void cpu_relax() { __builtin_ia32_pause(); }      // inside a spin loop
+#else
+inline void cpu_relax() { std::this_thread::yield(); }
+#endif
+
+// A buffer on the current device that grows on demand; its owner keeps the pointer and the capacity in bytes.
+// grow_buffer: room for `need` bytes (the contents are not kept).  drain: a stream whose work may still use the old block, waited
+// for before that is freed.  The caller words a failure: *failed (when given) names the call that returned it; after a failed
+// allocation the buffer is empty.  release_buffer: frees a block larger than `keep` bytes.
+template <class T> void release_buffer(T *&p, size_t &cap, size_t keep = 0)
+{
+    if (cap > keep) { (void)hipFree(p); p = nullptr; cap = 0; }
+}
+template <class T> hipError_t grow_buffer(T *&p, size_t &cap, size_t need, hipStream_t drain = nullptr, const char **failed = nullptr)
+{
+    if (need <= cap) return hipSuccess;
+    if (failed) *failed = "hipStreamSynchronize(drain)";
+    hipError_t e = drain ? hipStreamSynchronize(drain) : hipSuccess;
+    if (e != hipSuccess) return e;
+    release_buffer(p, cap);
+    if (failed) *failed = "device_alloc((void **)p, need)";
+    e = device_alloc(&p, need);
+    if (e != hipSuccess) p = nullptr; else cap = need;
+    return e;
+}
+
+// The finished tree (n nodes, 8 bytes of each array per node) from device memory into two host arrays from alloc(bytes), which
+// the library's caller frees with free().  On failure nothing is left allocated, `out` is untouched and the runtime's record is
+// cleared; *no_host_memory (when given) tells an allocation that failed from a copy that did.
+template <class Alloc>
+hipError_t tree_to_host(const void *d_structs, const void *d_values, size_t n, Alloc alloc, sdfhip_octdata *out, bool *no_host_memory = nullptr)
+{
+    int32_t *S = static_cast<int32_t *>(alloc(n * 8));
+    uint8_t *V = static_cast<uint8_t *>(alloc(n * 8));
+    if (no_host_memory) *no_host_memory = !(S && V);
+    hipError_t e = !(S && V) ? hipErrorOutOfMemory : hipMemcpy(S, d_structs, n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(V, d_values, n * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { (void)hipGetLastError(); free(S); free(V); return e; }
+    out->length = (uint32_t)n; out->structs = S; out->values = V;
+    return hipSuccess;
+}
+
+// device_memory.hip: the pool the builder's arenas take their chunks from and give them back to (device_alloc_bytes trims it when
+// the device is out of memory).  pool_take: a chunk of `want` bytes or somewhat more, its size in *size; null when the pool
+// holds none (or SDFHIP_GEN_POOL=0).
+void *pool_take(int device, size_t want, size_t *size);
+void pool_give(int device, void *base, size_t size);
+
+}  // namespace sdfhip

@@ -9,7 +9,7 @@
 // scene's own stream and wait.  The staging buffers cannot live in the scene handle (scene.h belongs to the renderer's measured
 // sources), so small ones are kept per device here and large ones live for the call.
 #include "query_kernels.h"
-#include "scene.h"
+#include "host_support.h"
 #include "abi_guard.h"
 
 #include <cmath>
@@ -136,19 +136,9 @@ Staging g_staging[MAX_DEVICES];
 
 int grow(void *&p, size_t &cap, size_t need, const char *what)
 {
-    if (need <= cap) return SDFHIP_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    if (device_alloc_bytes(&p, need) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %zu bytes of query records", what, need);
-    }
-    cap = need;
-    return SDFHIP_OK;
-}
-void shrink(void *&p, size_t &cap)
-{
-    if (cap > KEEP_BYTES) { (void)hipFree(p); p = nullptr; cap = 0; }
+    if (grow_buffer(p, cap, need) == hipSuccess) return SDFHIP_OK;
+    (void)hipGetLastError();
+    return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %zu bytes of query records", what, need);
 }
 
 // host records in -> launch -> host records out, on the scene's own stream.  launch(d_in, d_out) runs under the handle's lock.
@@ -175,8 +165,8 @@ int through_staging(sdfhip_scene *s, const char *what, const void *h_in, size_t 
         }();
         if (rc != SDFHIP_OK) (void)hipStreamSynchronize(st);      // nothing of this call is in flight when the buffers are handed on
     }
-    shrink(b.in, b.in_cap);
-    shrink(b.out, b.out_cap);
+    release_buffer(b.in, b.in_cap, KEEP_BYTES);
+    release_buffer(b.out, b.out_cap, KEEP_BYTES);
     return rc;
 }
 

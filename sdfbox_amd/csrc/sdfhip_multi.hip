@@ -23,6 +23,7 @@
 //
 // Everything here is written against the library's own C ABI (sdfhip_render_sparse_device, sdfhip_deinterleave_*): the
 // multi-device layer adds no kernel.
+#include "host_support.h"
 #include "abi_guard.h"
 
 #include <hip/hip_runtime.h>
@@ -48,14 +49,7 @@ constexpr uint32_t MAX_RANKS = 16;
 constexpr uint32_t MAX_SLOTS = 4;
 constexpr uint32_t MAX_GROUP = 8;          // frames per launch (sdfhip_render_batch_device's limit)
 
-#define M_TRY(expr)                                                                           \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                             \
-            (void)hipGetLastError();   /* the runtime's record of it: a later launch check must not report it as its own */ \
-            return fail(SDFHIP_ERR_DEVICE, "multi: %s failed: %s", #expr, hipGetErrorString(e_)); \
-        }                                                                                   \
-    } while (0)
+#define M_TRY(expr) HIP_TRY_AS("multi: ", expr, #expr)
 
 // ---- RCCL, loaded on demand ---------------------------------------------------------------------------------------
 struct Rccl {
@@ -113,11 +107,7 @@ struct Worker {
         for (;;) {
             for (int i = 0; i < 64; i++) {
                 if (a.load(std::memory_order_acquire) != seen || (stop && stop->load(std::memory_order_acquire))) return true;
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#else
-                std::this_thread::yield();
-#endif
+                cpu_relax();
             }
             if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(SPIN_US)) return false;
         }
@@ -267,12 +257,6 @@ struct sdfhip_multi {
 
 namespace {
 
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (hipSetDevice(d) != hipSuccess) (void)hipGetLastError(); }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 int nccl_fail(sdfhip_multi *m, int rc, const char *what)
 {
     return fail(SDFHIP_ERR_DEVICE, "multi: %s failed: %s", what, m->rccl.GetErrorString ? m->rccl.GetErrorString(rc) : "RCCL error");
@@ -300,11 +284,8 @@ hipError_t push(void *dst, int dst_dev, const void *src, int src_dev, size_t byt
 
 int grow(uint8_t **p, size_t *cap, size_t need, hipStream_t drain)
 {
-    if (need <= *cap) return SDFHIP_OK;
-    if (drain) M_TRY(hipStreamSynchronize(drain));
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    M_TRY(device_alloc((void **)p, need));
-    *cap = need;
+    const char *call = "";
+    HIP_TRY_AS("multi: ", grow_buffer(*p, *cap, need, drain, &call), call);
     return SDFHIP_OK;
 }
 
@@ -315,7 +296,7 @@ int rank_submit(void *arg, uint32_t r)
     const sdfhip_multi::Job &J = m->job;
     Slot &S = m->slots[J.slot];
     RankBuf &B = S.rb[r];
-    DevGuard g(m->devices[r]);
+    DeviceGuard g(m->devices[r]);
     const Layout &L = m->lay;
     if (L.bands[r].empty()) { B.sent = 0; return SDFHIP_OK; }              // more ranks than bands: nothing to do
     if (J.timed) M_TRY(hipEventRecord(B.ev_start, B.stream));
@@ -391,7 +372,7 @@ int prepare_slot(sdfhip_multi *m, Slot &S, uint32_t n_frames, bool path, bool in
     const Layout &L = m->lay;
     for (uint32_t r = 0; r < m->n; r++) {
         RankBuf &B = S.rb[r];
-        DevGuard g(m->devices[r]);
+        DeviceGuard g(m->devices[r]);
         if (path) {
             if (r > 0) { int rc = grow(&B.d_bands, &B.bands_cap, (size_t)n_frames * L.rows_per_rank * L.width * frame_px_bytes, B.stream); if (rc) return rc; }
         } else {
@@ -406,13 +387,13 @@ int prepare_slot(sdfhip_multi *m, Slot &S, uint32_t n_frames, bool path, bool in
                 B.count_base = 0;
             }
             if (r > 0 || m->rccl_self) {
-                DevGuard g0(m->devices[0]);
+                DeviceGuard g0(m->devices[0]);
                 rc = grow(&B.d_gather, &B.gather_cap, sh.bytes, S.rb[0].stream);
                 if (rc) return rc;
             }
         }
     }
-    DevGuard g0(m->devices[0]);
+    DeviceGuard g0(m->devices[0]);
     if (path) { int rc = grow(&S.d_dense, &S.dense_cap, (size_t)m->n * n_frames * L.rows_per_rank * L.width * frame_px_bytes, S.rb[0].stream); if (rc) return rc; }
     if (internal_frames) { int rc = grow(&S.d_frames, &S.frames_cap, (size_t)n_frames * L.width * L.height * frame_px_bytes, S.rb[0].stream); if (rc) return rc; }
     S.dirty = false;
@@ -423,7 +404,7 @@ int prepare_slot(sdfhip_multi *m, Slot &S, uint32_t n_frames, bool path, bool in
 int assemble(sdfhip_multi *m, Slot &S, int only_rank)
 {
     const Layout &L = m->lay;
-    DevGuard g0(m->devices[0]);
+    DeviceGuard g0(m->devices[0]);
     hipStream_t st = S.rb[0].stream;
     for (uint32_t r = 1; r < m->n; r++)
         if (!L.bands[r].empty() && (only_rank < 0 || (uint32_t)only_rank == r)) M_TRY(hipStreamWaitEvent(st, S.rb[r].ev_sent, 0));
@@ -445,7 +426,7 @@ int post_receives(sdfhip_multi *m, Slot &S)
 {
     if (!m->use_rccl || m->n == 1) return SDFHIP_OK;
     const Layout &L = m->lay;
-    DevGuard g0(m->devices[0]);
+    DeviceGuard g0(m->devices[0]);
     int e = m->rccl.GroupStart();
     if (e) return nccl_fail(m, e, "ncclGroupStart");
     for (uint32_t r = 1; r < m->n; r++) {
@@ -474,7 +455,7 @@ int abort_slot(sdfhip_multi *m, Slot &S, int rc)
     if (m->use_rccl && m->n > 1) m->broken = true;
     else {
         for (uint32_t r = 0; r < m->n; r++) {
-            DevGuard g(m->devices[r]);
+            DeviceGuard g(m->devices[r]);
             if (S.rb[r].stream) (void)hipStreamSynchronize(S.rb[r].stream);
         }
         (void)hipGetLastError();
@@ -528,7 +509,7 @@ int submit_locked(sdfhip_multi *m, uint32_t slot, const sdfhip_info *infos, uint
     if (rc == SDFHIP_OK) rc = on_all_ranks(m, rank_submit);
     if (rc == SDFHIP_OK) rc = assemble(m, S, -1);
     if (rc == SDFHIP_OK) {
-        DevGuard g0(m->devices[0]);
+        DeviceGuard g0(m->devices[0]);
         const hipError_t e = hipEventRecord(S.ev_done, S.rb[0].stream);
         if (e != hipSuccess) rc = fail(SDFHIP_ERR_DEVICE, "multi: queueing the frame's completion failed: %s", hipGetErrorString(e));
     }
@@ -542,7 +523,7 @@ int wait_body(sdfhip_multi *m, Slot &S, uint32_t &resent)
 {
     const Layout &L = m->lay;
     {
-        DevGuard g0(m->devices[0]);
+        DeviceGuard g0(m->devices[0]);
         M_TRY(hipEventSynchronize(S.ev_done));
     }
     if (!S.path) {
@@ -556,14 +537,14 @@ int wait_body(sdfhip_multi *m, Slot &S, uint32_t &resent)
             if ((r > 0 || m->rccl_self) && used > B.sent) {
                 // the share needed more floats than were sent with it: the tail now, and this rank's rows again
                 {
-                    DevGuard g(m->devices[r]);
+                    DeviceGuard g(m->devices[r]);
                     M_TRY(push(B.d_gather + sh.off_floats + (size_t)B.sent * 4, m->devices[0],
                                B.d_share + sh.off_floats + (size_t)B.sent * 4, m->devices[r], (size_t)(used - B.sent) * 4, B.stream));
                     M_TRY(hipEventRecord(B.ev_sent, B.stream));
                 }
                 int rc = assemble(m, S, (int)r);
                 if (rc != SDFHIP_OK) return rc;
-                DevGuard g0(m->devices[0]);
+                DeviceGuard g0(m->devices[0]);
                 M_TRY(hipStreamSynchronize(S.rb[0].stream));
                 resent++;
                 B.sent = used;
@@ -597,7 +578,7 @@ int wait_locked(sdfhip_multi *m, uint32_t slot, void **d_frames, sdfhip_multi_st
         stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - S.t_submit).count();
         for (uint32_t r = 0; r < m->n && r < 16; r++) {
             if (L.bands[r].empty()) continue;
-            DevGuard g(m->devices[r]);
+            DeviceGuard g(m->devices[r]);
             float ms = 0.0f;
             if (S.timed && hipEventElapsedTime(&ms, S.rb[r].ev_start, S.rb[r].ev_sent) == hipSuccess) stats->rank_ms[r] = ms;
             (void)hipGetLastError();
@@ -630,7 +611,7 @@ try {
         Slot &S = m->slots[k];
         for (uint32_t r = 0; r < m->n; r++) {
             RankBuf &B = S.rb[r];
-            DevGuard g(m->devices[r]);
+            DeviceGuard g(m->devices[r]);
             if (B.stream) (void)hipStreamSynchronize(B.stream);
             if (B.d_share) (void)hipFree(B.d_share);
             if (B.d_bands) (void)hipFree(B.d_bands);
@@ -638,7 +619,7 @@ try {
             if (B.ev_sent) (void)hipEventDestroy(B.ev_sent);
             if (B.stream) (void)hipStreamDestroy(B.stream);
         }
-        DevGuard g0(m->devices[0]);
+        DeviceGuard g0(m->devices[0]);
         for (uint32_t r = 0; r < m->n; r++) if (S.rb[r].d_gather) (void)hipFree(S.rb[r].d_gather);
         if (S.rx_stream) { (void)hipStreamSynchronize(S.rx_stream); (void)hipStreamDestroy(S.rx_stream); }
         if (S.d_frames) (void)hipFree(S.d_frames);
@@ -691,7 +672,7 @@ try {
         if (devices[r] == devices[0]) continue;
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, devices[r], devices[0]) != hipSuccess || !can) continue;      // hipMemcpyPeerAsync then stages through the host
-        DevGuard g(devices[r]);
+        DeviceGuard g(devices[r]);
         const hipError_t e = hipDeviceEnablePeerAccess(devices[0], 0);
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
         (void)hipGetLastError();
@@ -700,13 +681,13 @@ try {
         Slot &S = m->slots[k];
         for (uint32_t r = 0; r < n_devices; r++) {
             RankBuf &B = S.rb[r];
-            DevGuard g(devices[r]);
+            DeviceGuard g(devices[r]);
             hipError_t e;
             if ((e = hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking)) != hipSuccess ||
                 (e = hipEventCreate(&B.ev_start)) != hipSuccess || (e = hipEventCreate(&B.ev_sent)) != hipSuccess)
                 return bail(fail(SDFHIP_ERR_DEVICE, "multi_create: stream / event on device %d: %s", devices[r], hipGetErrorString(e)));
         }
-        DevGuard g0(devices[0]);
+        DeviceGuard g0(devices[0]);
         hipError_t e;
         if ((e = hipHostMalloc((void **)&S.h_counts, MAX_RANKS * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
             return bail(fail(SDFHIP_ERR_DEVICE, "multi_create: pinned memory: %s", hipGetErrorString(e)));
@@ -753,7 +734,7 @@ try {
     std::vector<uint8_t> pattern(BYTES), back(BYTES);
     Slot &S = m->slots[0];
     uint8_t *d_rx = nullptr;
-    { DevGuard g0(m->devices[0]); M_TRY(device_alloc((void **)&d_rx, BYTES)); }
+    { DeviceGuard g0(m->devices[0]); M_TRY(device_alloc((void **)&d_rx, BYTES)); }
     int rc = SDFHIP_OK;
     char first[256] = { 0 };
     for (uint32_t r = 0; r < m->n; r++) {
@@ -775,17 +756,17 @@ try {
             int ne = 0;
             float ms = 0.0f;
             {
-                DevGuard g(m->devices[r]);
+                DeviceGuard g(m->devices[r]);
                 RankBuf &B = S.rb[r];
                 if ((e = device_alloc((void **)&d_tx, BYTES)) == hipSuccess &&
                     (e = hipMemcpyAsync(d_tx, pattern.data(), BYTES, hipMemcpyHostToDevice, B.stream)) == hipSuccess) {
-                    { DevGuard g0(m->devices[0]); e = hipMemsetAsync(d_rx, 0, BYTES, S.rb[0].stream); if (e == hipSuccess) e = hipStreamSynchronize(S.rb[0].stream); }
+                    { DeviceGuard g0(m->devices[0]); e = hipMemsetAsync(d_rx, 0, BYTES, S.rb[0].stream); if (e == hipSuccess) e = hipStreamSynchronize(S.rb[0].stream); }
                     if (e == hipSuccess) e = hipEventRecord(B.ev_start, B.stream);
                     if (e == hipSuccess) {
                         if (m->use_rccl) {
                             // the gather's own pattern: the receive on devices[0]'s receive stream, the send on the rank's stream, each in a group
                             // (one group for both when the rank IS devices[0]: the self test of one-GPU boxes)
-                            DevGuard g0(m->devices[0]);
+                            DeviceGuard g0(m->devices[0]);
                             if (r == 0) {
                                 ne = m->rccl.GroupStart();
                                 if (!ne) ne = m->rccl.Send(d_tx, BYTES, NCCL_UINT8, 0, m->comms[0], B.stream);
@@ -795,7 +776,7 @@ try {
                                 ne = m->rccl.GroupStart();
                                 if (!ne) ne = m->rccl.Recv(d_rx, BYTES, NCCL_UINT8, (int)r, m->comms[0], S.rx_stream);
                                 if (!ne) ne = m->rccl.GroupEnd();
-                                DevGuard gr(m->devices[r]);
+                                DeviceGuard gr(m->devices[r]);
                                 if (!ne) ne = m->rccl.GroupStart();
                                 if (!ne) ne = m->rccl.Send(d_tx, BYTES, NCCL_UINT8, 0, m->comms[r], B.stream);
                                 if (!ne) ne = m->rccl.GroupEnd();
@@ -811,7 +792,7 @@ try {
                 if (d_tx) (void)hipFree(d_tx);
             }
             if (e == hipSuccess && !ne) {
-                DevGuard g0(m->devices[0]);
+                DeviceGuard g0(m->devices[0]);
                 if (m->use_rccl && r > 0) e = hipStreamSynchronize(S.rx_stream);
                 if (e == hipSuccess) e = hipMemcpy(back.data(), d_rx, BYTES, hipMemcpyDeviceToHost);
             }
@@ -832,7 +813,7 @@ try {
         }
         if (links) links[r] = L;
     }
-    { DevGuard g0(m->devices[0]); (void)hipFree(d_rx); }
+    { DeviceGuard g0(m->devices[0]); (void)hipFree(d_rx); }
     return rc == SDFHIP_OK ? SDFHIP_OK : fail(rc, "%s", first);
 }
 SDFHIP_ABI_CATCH(sdfhip_multi_selftest)
@@ -915,7 +896,7 @@ static int multi_render_host(sdfhip_multi *m, const sdfhip_info *info, const sdf
     rc = wait_locked(m, 0, &d, stats);
     if (rc != SDFHIP_OK) return rc;
     const size_t px = (flags & (SDFHIP_FLAG_DISPLAY | SDFHIP_FLAG_DISPLAY_DEBUG)) ? 4 : 16;
-    DevGuard g0(m->devices[0]);
+    DeviceGuard g0(m->devices[0]);
     M_TRY(hipMemcpyAsync(out, d, (size_t)width * height * px, hipMemcpyDeviceToHost, m->slots[0].rb[0].stream));
     M_TRY(hipStreamSynchronize(m->slots[0].rb[0].stream));
     if (stats) stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
