@@ -215,6 +215,21 @@ public:
         Check(sdfhip_scene_pick(scene, &state, pixels_xy.data(), (uint32_t)out.size(), max_steps, out.data()));
         return out;
     }
+    // Surface extraction (sdfhip_scene_mesh; nothing in the reference corresponds -- its tree only ever becomes pixels): the loaded
+    // model as a triangle soup, 3 vertices of six floats {position, normal} per triangle in a pinned order -- the layout of a point
+    // cloud, so the result feeds sdfhip_sdfgen[_scene] as it is.  level: -1 = the leaves, 0..12 = the level-of-detail mesh of that
+    // level.  Save it with sdfhip_mesh_save_ply / _obj on an sdfhip_mesh{n, data}
+    std::vector<float> Mesh(int level = -1, sdfhip_mesh_stats *stats = nullptr)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Mesh: no model loaded");
+        sdfhip_mesh_options opt;
+        sdfhip_mesh_options_default(&opt);
+        opt.level = level;
+        sdfhip_mesh mesh = { 0, nullptr };
+        Check(sdfhip_scene_mesh(scene, &opt, &mesh, stats));
+        struct Release { sdfhip_mesh &m; ~Release() { sdfhip_mesh_free(&m); } } release{ mesh };
+        return mesh.n_triangles ? std::vector<float>(mesh.verts6, mesh.verts6 + (size_t)mesh.n_triangles * 18) : std::vector<float>();
+    }
     // Draw's UpdateBuffer(info) + DispatchSized(W, H, 1), Program.cs:81,94 -> RGBA32F frame
     void Draw(const Info &state, int width, int height, std::vector<float> &frame, uint32_t flags = 0)
     {

@@ -553,6 +553,58 @@ SDFHIP_API int sdfhip_scene_raycast_device(sdfhip_scene *scene, const sdfhip_ray
 SDFHIP_API int sdfhip_scene_pick(sdfhip_scene *scene, const sdfhip_info *info, const uint32_t *pixels_xy, uint32_t n, uint32_t max_steps,
                                  sdfhip_hit *out);
 
+/* ---- surface extraction: a resident scene as triangles ------------------------------------------------
+ * Replaces: nothing in the reference's code -- its tree only ever becomes pixels.  A scene that was built, carved and picked here
+ * leaves as geometry: a triangle soup of 3 * n_triangles vertices of six floats {position, normal}, the layout of sdfhip_points.data,
+ * so a mesh goes straight back into sdfhip_sdfgen[_scene] and through sdfhip_load_ply / sdfhip_load_obj.  No index buffer.
+ * The rule, pinned (fp32, each operation rounded in the order written; DESIGN.md section 8 has it in full):
+ *   sign       a corner byte b decodes as (b/255 - 0.25) * 2S: the surface is at b = 63.75; inside <=> b <= 63
+ *   cells      level -1: the leaves; level L = 0..12: the leaves of depth <= L and the internal nodes of depth exactly L with their own
+ *              eight bytes (a level-of-detail mesh).  A cell emits triangles only if its bytes are mixed (min <= 63 < max).  Its integer
+ *              coordinates c of its depth d (edge S = 2^-d) come from the links: octant within the parent = index - parent.children
+ *   triangles  marching tetrahedra on the Kuhn decomposition: six tetrahedra {0, 1<<a0, 1<<a0 | 1<<a1, 7} round the diagonal 0-7, one
+ *              per axis permutation (a0, a1, a2) in lexicographic order.  Cut edges are pairs of local corners (i, j), i < j.  One or
+ *              three inside corners: one triangle of the three cut edges in ascending order; two inside i0 < i1 and two outside
+ *              o0 < o1: the quad (i0,o0) (i0,o1) (i1,o1) (i1,o0) as triangles (q0,q1,q2) (q0,q2,q3).  Every triangle is counter-clockwise
+ *              seen from outside (the last two vertices swapped where the unit tetrahedron with cuts at the edge midpoints asks for it)
+ *   vertex     on the edge from cube corner lo to hi: t = (63.75f - (float)b_lo) / ((float)b_hi - (float)b_lo), and per axis a
+ *              p_a = ((float)(c_a + bit_a(lo)) + (bit_a(hi) != bit_a(lo) ? t : 0.0f)) * S -- equal-depth neighbours with equal bytes
+ *              on a shared edge produce the same bits
+ *   normal     gradient() (Compute.hlsl:112-130) at that position with the cursor on the cell, times 1 / sqrt(dot(g, g)) as
+ *              sdfhip_hit.normal; a zero gradient gives NaN, as there
+ *   order      cells in ascending node index, tetrahedra and triangles as above: the bytes never depend on which wave finished first
+ * Cells of different depth meet in T-junctions (no crack patching); nothing is welded, clipped or simplified.
+ *   sdfhip_scene_mesh          the mesh in host memory (release with sdfhip_mesh_free), synchronous, on the scene's own stream
+ *   sdfhip_scene_mesh_device   ALWAYS returns the count the scene needs in *n_triangles (one host synchronisation on `stream`); writes
+ *                              the vertices to d_verts6 (device memory on the scene's device) only if the count fits
+ *                              capacity_triangles -- capacity 0 with a null pointer asks for the count -- asynchronously on `stream`
+ *                              (NULL = the HIP default stream): sdfhip_render_device's convention.  Runs beside frames that are
+ *                              already enqueued on other streams; the call holds the handle's lock while it waits for the count, so
+ *                              another host thread's call on the same scene (a render, a query, a mesh) waits for that round trip
+ *   sdfhip_mesh_save_ply       binary little-endian, the vertex element first (x y z nx ny nz floats), then faces as uchar / int lists
+ *                              (3i, 3i+1, 3i+2): sdfhip_load_ply reads the vertices back bit for bit
+ *   sdfhip_mesh_save_obj       `v` / `vn` lines with %.9g, then `f a//a b//b c//c`: sdfhip_load_obj gives the same vertices back
+ * opt: NULL = defaults (level -1); the struct grows like sdfhip_upload_options (size set by sdfhip_mesh_options_default; a larger,
+ * newer struct is accepted when the fields this library does not know are all -1).
+ * SDFHIP_ERR_ARG: a null scene or output, level outside -1..12, an options struct the size rules refuse, a capacity without a buffer, a
+ * result of more than 2^31 - 1 triangles; SDFHIP_ERR_BAD_TREE: the tree is not consistent (stack_kernel_ok == 0 in sdfhip_scene_info), as
+ * sdfhip_scene_edit refuses it; SDFHIP_ERR_NOMEM: out of device or host memory (nothing leaks, the scene is untouched).  A scene that
+ * cuts nowhere is a success with zero triangles (verts6 NULL). */
+typedef struct sdfhip_mesh_options { uint32_t size; int32_t level; } sdfhip_mesh_options;
+typedef struct sdfhip_mesh { uint32_t n_triangles; float *verts6; } sdfhip_mesh;      /* 3 * n_triangles x 6 floats */
+typedef struct sdfhip_mesh_stats {
+    uint32_t nodes, cells, cells_cut, n_triangles;   /* cells: the cell set of the level; cells_cut: those with mixed bytes */
+    float kernel_ms;                                 /* HIP events around the count, scan and emit kernels */
+    float total_ms;                                  /* host clock, the whole call */
+} sdfhip_mesh_stats;
+SDFHIP_API void sdfhip_mesh_options_default(sdfhip_mesh_options *opt);
+SDFHIP_API int sdfhip_scene_mesh(sdfhip_scene *scene, const sdfhip_mesh_options *opt, sdfhip_mesh *out, sdfhip_mesh_stats *stats);
+SDFHIP_API int sdfhip_scene_mesh_device(sdfhip_scene *scene, const sdfhip_mesh_options *opt, float *d_verts6, uint32_t capacity_triangles,
+                                        uint32_t *n_triangles, void *stream);
+SDFHIP_API void sdfhip_mesh_free(sdfhip_mesh *mesh);
+SDFHIP_API int sdfhip_mesh_save_ply(const sdfhip_mesh *mesh, const char *path);
+SDFHIP_API int sdfhip_mesh_save_obj(const sdfhip_mesh *mesh, const char *path);
+
 /* ---- one frame over several GPUs, behind one call -----------------------------------------------------------
  * Replaces: Program.Draw's UpdateBuffer(info) + DispatchSized(W, H, 1) (SdfBox/Program.cs:81,94) when the frame is rendered by
  * the GPUs of a node: the host still makes ONE call per frame.  One process; the scene is replicated on every device at

@@ -50,7 +50,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import COctData, CPoints, Edit, EditStats, Hit, Info, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CPoints, Edit, EditStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -178,6 +178,23 @@ else:
     assert (ctypes.sizeof(Probe), ctypes.sizeof(Ray), ctypes.sizeof(Hit)) == (32, 32, 48)
 
 
+    class MeshOptions(ctypes.Structure):
+        """sdfhip_mesh_options: level -1 = the leaves (full detail), 0..12 = the level-of-detail mesh of that level."""
+        _fields_ = [("size", ctypes.c_uint32), ("level", ctypes.c_int32)]
+
+        def __init__(self, level=-1):
+            super().__init__(ctypes.sizeof(type(self)), int(level))
+
+
+    class CMesh(ctypes.Structure):
+        _fields_ = [("n_triangles", ctypes.c_uint32), ("verts6", ctypes.POINTER(ctypes.c_float))]
+
+
+    class MeshStats(ctypes.Structure):
+        _fields_ = [("nodes", ctypes.c_uint32), ("cells", ctypes.c_uint32), ("cells_cut", ctypes.c_uint32), ("n_triangles", ctypes.c_uint32),
+                    ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
     class SdfHipError(RuntimeError):
         def __init__(self, code, message):
             super().__init__(f"sdfhip error {code}: {message}")
@@ -247,6 +264,12 @@ _SIG = {
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),
     "sdfhip_scene_raycast_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_pick": (_c.c_int, [_vp, _c.POINTER(Info), _vp, _c.c_uint32, _c.c_uint32, _vp]),
+    "sdfhip_mesh_options_default": (None, [_c.POINTER(MeshOptions)]),
+    "sdfhip_scene_mesh": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _c.POINTER(CMesh), _c.POINTER(MeshStats)]),
+    "sdfhip_scene_mesh_device": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp]),
+    "sdfhip_mesh_free": (None, [_c.POINTER(CMesh)]),
+    "sdfhip_mesh_save_ply": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
+    "sdfhip_mesh_save_obj": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
     "sdfhip_scene_top_grid": (_c.c_int, [_vp, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_uint64)]),
     "sdfhip_render_bands_device": (_c.c_int, [_vp, _c.POINTER(Info), _c.c_uint32, _c.POINTER(PathTrace), _c.c_uint32,
                                               _c.c_uint32, _c.c_uint32, _c.POINTER(_c.c_uint16), _c.c_uint32,

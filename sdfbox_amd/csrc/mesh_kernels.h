@@ -1,0 +1,322 @@
+// Surface extraction from a resident scene (gfx950): marching tetrahedra on the Kuhn decomposition of every cell whose bytes are
+// mixed, as a triangle soup of {position, normal} vertices in a pinned order.  Non-template helpers and three kernels: included by
+// mesh.hip ONLY.  Host side, C ABI: mesh.hip; the writers: mesh_io.cpp.
+//
+// Replaces: nothing in the reference's code -- its tree only ever becomes pixels.
+//
+// The rule is the contract of include/sdfhip.h (sdfhip_scene_mesh) and DESIGN.md section 8 (N7): fp32, each operation rounded on its
+// own, in the order written (-ffp-contract=off); tests/mesh_restatement.py restates it with numpy, node for node.  The normal is
+// raymarch_device.h's gradient(), untouched, with the cell as the cursor's cell.
+//
+// The order (cells by node index, then tetrahedron, then triangle) must not depend on which wave finished first, so the pass is
+// count -> scan -> emit, and both ends stream the records:
+//   k_mesh_count   one lane per node, MESH_CHUNK nodes per workgroup: one 16-byte load gives links and bytes; the chunk's triangle
+//                  total goes to chunk[]; cells and cut cells are counted beside it
+//   k_mesh_scan    the chunks' totals -> exclusive prefix (one workgroup), and the grand total as 64 bits
+//   k_mesh_emit    the same lanes read the same records again, recount, take their offset from the chunk's prefix and a scan inside
+//                  the workgroup (shuffles within a wave, LDS across the four), and the lanes whose cell is cut walk up the parent
+//                  links for their coordinates (at most 12 dependent 8-byte loads) and write their triangles
+// Reading the records twice (2 x 16 bytes per node) is cheaper than a per-node count array written, scanned and read back, and
+// keeps the temporary memory at four bytes per 1024 nodes.
+#pragma once
+#include "raymarch_device.h"
+
+namespace sdfhip {
+
+constexpr int MESH_THREADS = 256;
+constexpr int MESH_ROWS = 4;                                  // rows of MESH_THREADS consecutive nodes per workgroup
+constexpr uint32_t MESH_CHUNK = MESH_THREADS * MESH_ROWS;
+constexpr int MESH_MAX_DEPTH = LM;                            // the deepest tree the walk is sized for (checked by the host side)
+
+// what the passes count beside the triangles: 64-bit triangle total (k_mesh_scan), cells of the level, cells whose bytes are mixed
+struct MeshHeader { unsigned long long n_triangles; uint32_t cells, cells_cut; };
+
+// The six tetrahedra round the diagonal 0-7, one per axis permutation in lexicographic order: corners {0, v1, v2, 7} with
+// v1 = 1 << a0, v2 = v1 | 1 << a1.  Packed four bits per local corner.
+__device__ __forceinline__ uint32_t tet_corners(int t)
+{
+    // (x,y,z) 0137  (x,z,y) 0157  (y,x,z) 0237  (y,z,x) 0267  (z,x,y) 0457  (z,y,x) 0467
+    const uint32_t v1 = 0x442211u, v2 = 0x656353u;
+    return 0x7000u | (((v2 >> (4 * t)) & 7u) << 8) | (((v1 >> (4 * t)) & 7u) << 4);
+}
+
+// The triangles of (tetrahedron, inside mask): bits 0-1 their number; vertex k of the (up to) six at bits 4 + 4k: the cut edge's
+// local corners i (bits 0-1) < j (bits 2-3).  Cut edges in ascending (i, j) order for one or three inside corners, the quad
+// (i0,o0) (i0,o1) (i1,o1) (i1,o0) split along its first diagonal for two; the last two vertices of a triangle swapped where the
+// orientation test on the unit tetrahedron with cuts at the edge midpoints asks for it (counter-clockwise seen from outside:
+// dot(cross(p1 - p0, p2 - p0), mean(outside corners) - mean(inside corners)) > 0).  Worked out once from that rule; the
+// restatement derives its own and the GPU tests compare the vertices.
+static __device__ const uint32_t MESH_TRIANGLES[6 * 16] = {
+    0x0000000u, 0x000c841u, 0x0009d41u, 0x9d8dc82u, 0x000e981u, 0xe94ce42u, 0x8e4ed42u, 0x000edc1u, 0x000dec1u, 0xde4e842u, 0xec49e42u, 0x0009e81u, 0xcd8d982u, 0x000d941u, 0x0008c41u, 0x0000000u,
+    0x0000000u, 0x0008c41u, 0x000d941u, 0xd98cd82u, 0x0009e81u, 0x9e4ec42u, 0xe84de42u, 0x000dec1u, 0x000edc1u, 0xed48e42u, 0xce4e942u, 0x000e981u, 0xdc89d82u, 0x0009d41u, 0x000c841u, 0x0000000u,
+    0x0000000u, 0x0008c41u, 0x000d941u, 0xd98cd82u, 0x0009e81u, 0x9e4ec42u, 0xe84de42u, 0x000dec1u, 0x000edc1u, 0xed48e42u, 0xce4e942u, 0x000e981u, 0xdc89d82u, 0x0009d41u, 0x000c841u, 0x0000000u,
+    0x0000000u, 0x000c841u, 0x0009d41u, 0x9d8dc82u, 0x000e981u, 0xe94ce42u, 0x8e4ed42u, 0x000edc1u, 0x000dec1u, 0xde4e842u, 0xec49e42u, 0x0009e81u, 0xcd8d982u, 0x000d941u, 0x0008c41u, 0x0000000u,
+    0x0000000u, 0x000c841u, 0x0009d41u, 0x9d8dc82u, 0x000e981u, 0xe94ce42u, 0x8e4ed42u, 0x000edc1u, 0x000dec1u, 0xde4e842u, 0xec49e42u, 0x0009e81u, 0xcd8d982u, 0x000d941u, 0x0008c41u, 0x0000000u,
+    0x0000000u, 0x0008c41u, 0x000d941u, 0xd98cd82u, 0x0009e81u, 0x9e4ec42u, 0xe84de42u, 0x000dec1u, 0x000edc1u, 0xed48e42u, 0xce4e942u, 0x000e981u, 0xdc89d82u, 0x0009d41u, 0x000c841u, 0x0000000u,
+};
+
+// bit k: corner k is inside (byte <= 63; the surface is at 63.75, which no byte equals)
+__device__ __forceinline__ uint32_t inside_bits(uint32_t v0, uint32_t v1)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        m |= (((v0 >> (8 * k)) & 0xFFu) <= 63u ? 1u : 0u) << k;
+        m |= (((v1 >> (8 * k)) & 0xFFu) <= 63u ? 1u : 0u) << (4 + k);
+    }
+    return m;
+}
+// the four inside bits of tetrahedron t's local corners
+__device__ __forceinline__ uint32_t tet_mask(uint32_t in8, int t)
+{
+    const uint32_t c = tet_corners(t);
+    return (in8 & 1u) | (((in8 >> ((c >> 4) & 7u)) & 1u) << 1) | (((in8 >> ((c >> 8) & 7u)) & 1u) << 2) | (((in8 >> 7) & 1u) << 3);
+}
+// triangles of a cell with these inside bits: per tetrahedron 1 for one or three inside corners, 2 for two
+__device__ __forceinline__ uint32_t cell_triangles(uint32_t in8)
+{
+    uint32_t n = 0;
+#pragma unroll
+    for (int t = 0; t < 6; t++) {
+        const uint32_t pc = (uint32_t)__popc(tet_mask(in8, t));
+        n += pc == 2u ? 2u : (pc & 1u);
+    }
+    return n;
+}
+
+// depth of node i: the links up to the root (mixed nodes of a level >= 0 pass only)
+__device__ __forceinline__ int node_depth(const NodeRec *__restrict__ nodes, uint32_t n, int32_t parent)
+{
+    int d = 0;
+    while (parent >= 0 && (uint32_t)parent < n && d <= MESH_MAX_DEPTH) {
+        parent = (int32_t)nodes[parent].x;
+        d++;
+    }
+    return d;
+}
+
+// is node (children, depth) a cell of `level`: -1 = the leaves; L = the leaves of depth <= L and the internal nodes of depth L
+__device__ __forceinline__ bool is_cell(int32_t children, int level, int depth)
+{
+    const bool leaf = children < 0;
+    return level < 0 ? leaf : (leaf ? depth <= level : depth == level);
+}
+
+// A node's triangle count, and whether it is a cell and a cut one (for the statistics)
+__device__ __forceinline__ uint32_t node_triangles(const NodeRec *__restrict__ nodes, uint32_t n, const NodeRec &r, int level, bool &cell, bool &cut)
+{
+    const uint32_t in8 = inside_bits(r.z, r.w);
+    const bool mixed = in8 != 0u && in8 != 0xFFu;
+    // (the statistics count the level's cells, so for a level >= 0 the flat nodes walk for their depth too)
+    cell = level < 0 ? (int32_t)r.y < 0 : is_cell((int32_t)r.y, level, node_depth(nodes, n, (int32_t)r.x));
+    cut = cell && mixed;
+    return cut ? cell_triangles(in8) : 0u;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+// inclusive prefix sum over the wave's lanes
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= (uint32_t)o) v += u;
+    }
+    return v;
+}
+
+// STATS: also count the level's cells and cut cells into the header (the flat nodes of a level >= 0 then walk for their depth too)
+template <bool STATS>
+__global__ __launch_bounds__(MESH_THREADS) void k_mesh_count(const NodeRec *__restrict__ nodes, uint32_t n, int level, uint32_t *__restrict__ chunk,
+                                                             MeshHeader *__restrict__ head)
+{
+    __shared__ uint32_t part[3][MESH_THREADS / 64];
+    const uint32_t base = blockIdx.x * MESH_CHUNK + threadIdx.x;
+    NodeRec r[MESH_ROWS];
+#pragma unroll
+    for (int k = 0; k < MESH_ROWS; k++) {
+        const uint32_t i = base + (uint32_t)k * MESH_THREADS;
+        r[k] = i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);          // past the end: internal, flat, no cell of any level
+    }
+    uint32_t tris = 0, cells = 0, cuts = 0;
+#pragma unroll
+    for (int k = 0; k < MESH_ROWS; k++) {
+        const uint32_t i = base + (uint32_t)k * MESH_THREADS;
+        if (i >= n) continue;
+        bool cell = false, cut = false;
+        if (STATS || level < 0) {
+            tris += node_triangles(nodes, n, r[k], level, cell, cut);
+        } else {
+            const uint32_t in8 = inside_bits(r[k].z, r[k].w);
+            if (in8 != 0u && in8 != 0xFFu && is_cell((int32_t)r[k].y, level, node_depth(nodes, n, (int32_t)r[k].x))) tris += cell_triangles(in8);
+        }
+        cells += cell ? 1u : 0u; cuts += cut ? 1u : 0u;
+    }
+    tris = wave_sum(tris);
+    if (STATS) { cells = wave_sum(cells); cuts = wave_sum(cuts); }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) { part[0][wave] = tris; part[1][wave] = cells; part[2][wave] = cuts; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        chunk[blockIdx.x] = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        if (STATS) {
+            const uint32_t c = part[1][0] + part[1][1] + part[1][2] + part[1][3], u = part[2][0] + part[2][1] + part[2][2] + part[2][3];
+            if (c) atomicAdd(&head->cells, c);
+            if (u) atomicAdd(&head->cells_cut, u);
+        }
+    }
+}
+
+// the chunks' totals -> exclusive prefix in place, in one workgroup (at most 2^21 chunks: 2^31 nodes); sums in 64 bits -- the low
+// words are the offsets the emit uses, which the host side only launches when the total fits 31 bits
+__global__ __launch_bounds__(1024) void k_mesh_scan(uint32_t *__restrict__ chunk, uint32_t nchunk, MeshHeader *__restrict__ head)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
+    unsigned long long sum = 0;
+    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024; o <<= 1) {          // inclusive scan of the threads' sums (Hillis-Steele), as k_edit_scan_chunks
+        const unsigned long long v = t >= o ? part[t - o] : 0ull;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    unsigned long long run = part[t] - sum;
+    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = (uint32_t)run; run += v; }
+    if (t == 1023) head->n_triangles = part[1023];
+}
+
+// A triangle is 72 bytes, so triangle k starts 8 bytes past a 16-byte boundary when k is odd: 16-byte stores with one 8-byte store in
+// front (odd) or behind (even).  WIDE = false: nine 8-byte stores; NT = true: non-temporal stores, as the query records
+// (query_kernels.h) -- both measured slower here (mesh.hip has the figures) and kept for the A/B.
+template <bool NT> __device__ __forceinline__ void store2(float *p, float a, float b)
+{
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    if (NT) __builtin_nontemporal_store((f32x2){a, b}, reinterpret_cast<f32x2 *>(p));
+    else *reinterpret_cast<f32x2 *>(p) = (f32x2){a, b};
+}
+template <bool NT> __device__ __forceinline__ void store4(float *p, float a, float b, float c, float d)
+{
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    if (NT) __builtin_nontemporal_store((f32x4){a, b, c, d}, reinterpret_cast<f32x4 *>(p));
+    else *reinterpret_cast<f32x4 *>(p) = (f32x4){a, b, c, d};
+}
+template <bool NT, bool WIDE>
+__device__ __forceinline__ void store_triangle(float *__restrict__ verts6, uint32_t tri, const float (&f)[18])
+{
+    float *p = verts6 + (size_t)tri * 18;
+    if (!WIDE) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) store2<NT>(p + 2 * k, f[2 * k], f[2 * k + 1]);
+    } else if (tri & 1u) {
+        store2<NT>(p, f[0], f[1]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) store4<NT>(p + 2 + 4 * k, f[2 + 4 * k], f[3 + 4 * k], f[4 + 4 * k], f[5 + 4 * k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) store4<NT>(p + 4 * k, f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+        store2<NT>(p + 16, f[16], f[17]);
+    }
+}
+
+// The vertex on the cut edge from cube corner lo to cube corner hi (the bits of lo are a subset of hi's) of the cell with integer
+// coordinates (cx, cy, cz) of its depth, edge S: position, then gradient() there times 1 / sqrt(dot(g, g)), as sdfhip_hit.normal
+__device__ __forceinline__ void cut_vertex(const Cell &cell, uint32_t cx, uint32_t cy, uint32_t cz, uint32_t lo, uint32_t hi, float *o)
+{
+    const unsigned long long bytes = ((unsigned long long)cell.v1 << 32) | cell.v0;
+    const float b_lo = (float)(uint32_t)((bytes >> (8u * lo)) & 0xFFull), b_hi = (float)(uint32_t)((bytes >> (8u * hi)) & 0xFFull);
+    const float t = (63.75f - b_lo) / (b_hi - b_lo);
+    const uint32_t d = lo ^ hi;
+    const float px = ((float)(cx + (lo & 1u)) + ((d & 1u) ? t : 0.0f)) * cell.scale;
+    const float py = ((float)(cy + ((lo >> 1) & 1u)) + ((d & 2u) ? t : 0.0f)) * cell.scale;
+    const float pz = ((float)(cz + ((lo >> 2) & 1u)) + ((d & 4u) ? t : 0.0f)) * cell.scale;
+    float gx, gy, gz;
+    gradient(cell, px, py, pz, gx, gy, gz);
+    const float rg = 1.0f / sqrtf(dot3(gx, gy, gz, gx, gy, gz));
+    o[0] = px; o[1] = py; o[2] = pz; o[3] = gx * rg; o[4] = gy * rg; o[5] = gz * rg;
+}
+
+// chunk[]: the exclusive prefix k_mesh_scan left.  Every lane stays in the kernel through the workgroup's scans; only the vertex work
+// is under the lane's own condition.
+template <bool NT, bool WIDE>
+__global__ __launch_bounds__(MESH_THREADS) void k_mesh_emit(const NodeRec *__restrict__ nodes, uint32_t n, int level, const uint32_t *__restrict__ chunk,
+                                                            float *__restrict__ verts6)
+{
+    __shared__ uint32_t part[MESH_ROWS][MESH_THREADS / 64];
+    const uint32_t base = blockIdx.x * MESH_CHUNK + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    NodeRec r[MESH_ROWS];
+#pragma unroll
+    for (int k = 0; k < MESH_ROWS; k++) {
+        const uint32_t i = base + (uint32_t)k * MESH_THREADS;
+        r[k] = i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+    }
+    uint32_t cnt[MESH_ROWS], incl[MESH_ROWS];
+#pragma unroll
+    for (int k = 0; k < MESH_ROWS; k++) {
+        const uint32_t i = base + (uint32_t)k * MESH_THREADS;
+        const uint32_t in8 = inside_bits(r[k].z, r[k].w);
+        cnt[k] = 0u;
+        if (i < n && in8 != 0u && in8 != 0xFFu &&
+            (level < 0 ? (int32_t)r[k].y < 0 : is_cell((int32_t)r[k].y, level, node_depth(nodes, n, (int32_t)r[k].x))))
+            cnt[k] = cell_triangles(in8);
+        incl[k] = wave_scan(cnt[k]);
+        if (lane == 63u) part[k][wave] = incl[k];
+    }
+    __syncthreads();
+    uint32_t run = chunk[blockIdx.x];                     // the first triangle of this row's first wave
+#pragma unroll
+    for (int k = 0; k < MESH_ROWS; k++) {
+        uint32_t first = run + incl[k] - cnt[k];
+#pragma unroll
+        for (uint32_t w = 0; w < MESH_THREADS / 64; w++) {
+            if (w < wave) first += part[k][w];
+            run += part[k][w];
+        }
+        if (cnt[k] == 0u) continue;
+        // the cell's coordinates of its depth, from the links: the octant within the parent is index - parent.children
+        uint32_t cur = base + (uint32_t)k * MESH_THREADS, cx = 0, cy = 0, cz = 0;
+        int32_t parent = (int32_t)r[k].x;
+        int depth = 0;
+        while (parent >= 0 && (uint32_t)parent < n && depth <= MESH_MAX_DEPTH) {
+            const uint2 p = *reinterpret_cast<const uint2 *>(nodes + parent);        // {its parent, its children}
+            const uint32_t oct = cur - p.y;
+            cx |= (oct & 1u) << depth; cy |= ((oct >> 1) & 1u) << depth; cz |= ((oct >> 2) & 1u) << depth;
+            cur = (uint32_t)parent;
+            parent = (int32_t)p.x;
+            depth++;
+        }
+        Cell cell;
+        cell.scale = __int_as_float((127 - depth) << 23);                           // 2^-depth
+        cell.inv = __int_as_float((127 + depth) << 23);
+        cell.lx = (float)cx * cell.scale; cell.ly = (float)cy * cell.scale; cell.lz = (float)cz * cell.scale;       // exact
+        cell.v0 = r[k].z; cell.v1 = r[k].w;
+        const uint32_t in8 = inside_bits(r[k].z, r[k].w);
+        for (int t = 0; t < 6; t++) {
+            const uint32_t corners = tet_corners(t);
+            const uint32_t e = MESH_TRIANGLES[t * 16 + (int)tet_mask(in8, t)];
+            const uint32_t nt = e & 3u;
+            for (uint32_t j = 0; j < nt; j++) {
+                float f[18];
+#pragma unroll
+                for (int v = 0; v < 3; v++) {
+                    const uint32_t ij = (e >> (4u + 4u * (3u * j + (uint32_t)v))) & 15u;
+                    const uint32_t lo = (corners >> (4u * (ij & 3u))) & 7u, hi = (corners >> (4u * (ij >> 2))) & 7u;
+                    cut_vertex(cell, cx, cy, cz, lo, hi, f + 6 * v);
+                }
+                store_triangle<NT, WIDE>(verts6, first, f);
+                first++;
+            }
+        }
+    }
+}
+
+}  // namespace sdfhip

@@ -175,6 +175,32 @@ class Scene:
         check(lib.sdfhip_scene_raycast_device(self._h, ctypes.c_void_p(int(rays_ptr)), int(n), float(margin), float(limit), int(max_steps),
                                               ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(stream)) if stream else None))
 
+    # -- surface extraction (sdfhip_scene_mesh): the scene as triangles ----------------------------------------------------------
+    def Mesh(self, level=-1, want_stats=True):
+        """The surface as a triangle soup: an (n, 3, 6) float32 array {position, normal} per vertex -- reshape(-1, 6) is a point cloud
+        for FromPoints / OctData.SdfGen -- in the pinned order (cells by node index).  level: -1 = the leaves, 0..12 = the
+        level-of-detail mesh of that level.  Returns (triangles, MeshStats), or the array alone with want_stats=False."""
+        opt = _lib.MeshOptions(level)
+        raw = _lib.CMesh()
+        st = _lib.MeshStats()
+        check(lib.sdfhip_scene_mesh(self._h, ctypes.byref(opt), ctypes.byref(raw), ctypes.byref(st) if want_stats else None))
+        try:
+            n = raw.n_triangles
+            tris = np.ctypeslib.as_array(raw.verts6, shape=(n, 3, 6)).copy() if n else np.zeros((0, 3, 6), np.float32)
+        finally:
+            lib.sdfhip_mesh_free(ctypes.byref(raw))
+        return (tris, st) if want_stats else tris
+
+    def MeshDevice(self, out_ptr=None, capacity=0, level=-1, stream=None):
+        """The triangle count the scene needs at `level` -- always -- and, if it fits `capacity` triangles, the vertices into device
+        memory at `out_ptr` (capacity x 3 x 6 floats), asynchronously on `stream` (a raw hipStream_t value or None), as DrawDevice.
+        MeshDevice() asks for the count alone."""
+        opt = _lib.MeshOptions(level)
+        n = ctypes.c_uint32()
+        check(lib.sdfhip_scene_mesh_device(self._h, ctypes.byref(opt), ctypes.c_void_p(int(out_ptr)) if out_ptr else None, int(capacity),
+                                           ctypes.byref(n), ctypes.c_void_p(int(stream)) if stream else None))
+        return n.value
+
     def close(self):
         if self._h:
             lib.sdfhip_scene_free(self._h)
@@ -408,6 +434,27 @@ class MultiScene:
     def debug_floats_sent(self, floats):
         _lib.need_lab("MultiScene.debug_floats_sent")
         check(lib.sdfhip_multi_debug_floats_sent(self._h, int(floats)))
+
+
+def _as_mesh(triangles):
+    t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 3, 6)
+    raw = _lib.CMesh(len(t), t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    return t, raw
+
+
+def SaveMeshPly(path, triangles):
+    """(n, 3, 6) float32 triangles -> binary little-endian .ply, vertices {x y z nx ny nz} then faces (sdfhip_mesh_save_ply):
+    OctData.LoadPly reads the vertices back."""
+    import os
+    keep, raw = _as_mesh(triangles)
+    check(lib.sdfhip_mesh_save_ply(ctypes.byref(raw), os.fsencode(path)))
+
+
+def SaveMeshObj(path, triangles):
+    """(n, 3, 6) float32 triangles -> .obj with `v`, `vn` (%.9g) and `f a//a b//b c//c` lines (sdfhip_mesh_save_obj)."""
+    import os
+    keep, raw = _as_mesh(triangles)
+    check(lib.sdfhip_mesh_save_obj(ctypes.byref(raw), os.fsencode(path)))
 
 
 def device_pci_bus_id(device=0):
