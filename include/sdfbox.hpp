@@ -230,6 +230,23 @@ public:
         struct Release { sdfhip_mesh &m; ~Release() { sdfhip_mesh_free(&m); } } release{ mesh };
         return mesh.n_triangles ? std::vector<float>(mesh.verts6, mesh.verts6 + (size_t)mesh.n_triangles * 18) : std::vector<float>();
     }
+    // Triangle mesh -> model (sdfhip_trimesh_prepare + sdfhip_trimesh_build; nothing in the live reference corresponds -- the intent of its
+    // abandoned GpuGenerator.cs): verts6 = 3 * n vertices of six floats as Mesh() returns them (normals ignored), counter-clockwise seen
+    // from outside; the exact signed distance field becomes the loaded model, placed where the coordinates say (fit = false) or fitted
+    // into the cube.  The tree never leaves HBM.
+    void LoadTriangles(const std::vector<float> &verts6, int depth, bool fit = false, sdfhip_trimesh_stats *stats = nullptr)
+    {
+        sdfhip_trimesh_options opt;
+        sdfhip_trimesh_options_default(&opt);
+        opt.fit = fit ? 1 : 0;
+        sdfhip_trimesh mesh = {};
+        Check(sdfhip_trimesh_prepare(verts6.data(), (uint32_t)(verts6.size() / 18), 6, &opt, &mesh));
+        struct Release { sdfhip_trimesh &m; ~Release() { sdfhip_trimesh_free(&m); } } release{ mesh };
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_trimesh_build(device, &mesh, depth, &fresh, nullptr, stats));
+        if (scene) sdfhip_scene_free(scene);
+        scene = fresh;
+    }
     // Draw's UpdateBuffer(info) + DispatchSized(W, H, 1), Program.cs:81,94 -> RGBA32F frame
     void Draw(const Info &state, int width, int height, std::vector<float> &frame, uint32_t flags = 0)
     {

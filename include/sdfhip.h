@@ -605,6 +605,83 @@ SDFHIP_API void sdfhip_mesh_free(sdfhip_mesh *mesh);
 SDFHIP_API int sdfhip_mesh_save_ply(const sdfhip_mesh *mesh, const char *path);
 SDFHIP_API int sdfhip_mesh_save_obj(const sdfhip_mesh *mesh, const char *path);
 
+/* ---- triangle mesh -> ASDF: exact signed distance on the GPU ------------------------------------------
+ * Replaces: nothing in the live reference -- SdfGen builds from the nearest POINT of a cloud (dllmain.cpp:117-161), which
+ * sdfhip_sdfgen restates.  It is the intent of the reference's abandoned per-triangle GPU generator (SdfBox/GpuGenerator.cs +
+ * Shaders/Distancer.hlsl, SURVEY C10, which never ran) with the sign rule of the paper its README names as a main reference:
+ * Baerentzen & Aanaes, "Signed distance computation using the angle weighted pseudonormal".
+ *   sdfhip_load_ply_mesh / _obj_mesh   a file WITH its faces into an sdfhip_mesh (release with sdfhip_mesh_free): the format limits of
+ *                              sdfhip_load_ply / _obj (binary little-endian ply, vertex element first, six floats per vertex, then a
+ *                              `property list uchar int` face element; obj: v / vn / f, `#`, o, s, vt skipped) with faces as
+ *                              `a`, `a/b`, `a//c`, `a/b/c`, negative (relative) indices, polygons fanned from their first vertex
+ *                              (0, i, i+1); a vertex's normal is the file's where it has one, else 0.  They read what
+ *                              sdfhip_mesh_save_ply / _obj wrote bit for bit.  SDFHIP_ERR_IO: truncated or malformed.
+ *   sdfhip_trimesh_prepare     host: n_triangles x 3 vertices of `stride` 3 or 6 floats (6 = sdfhip_mesh.verts6, normals ignored),
+ *                              counter-clockwise seen from outside, into records (release with sdfhip_trimesh_free)
+ *   sdfhip_trimesh_build       GPU: records -> a resident scene and / or host arrays; the tree leaves HBM only for host_out
+ * prepare, pinned.  fit = 0 (default): coordinates as given, so the mesh of a scene lands where the scene was.  fit = 1: fp32, per
+ * axis mid = (lo + hi) * 0.5f of the bounding box, ext = the largest hi - lo, s = fill / ext (fill default 0.8),
+ * p' = (p - mid) * s + 0.5f; scale = s and offset = mid are reported (fit = 0: 1 and 0).  Then -0 becomes +0, and vertices are
+ * welded when their fp32 bits are equal; an edge is the unordered pair of welded vertices.  A triangle whose area in double is 0 or
+ * below 2^-40 of its longest edge squared is dropped and counted.  Normals, all in double from the fp32 positions, normalised, rounded
+ * to fp32: face = cross(b - a, c - a); edge pseudonormal = the sum of the unit normals of the faces on that edge; vertex
+ * pseudonormal = sum of angle * unit face normal, angle = atan2(|u x v|, u . v) of the triangle's two edges at the vertex; a zero
+ * sum falls back to the triangle's own face normal.  A record is 32 floats (128 bytes): a b c | face normal | pseudonormals of edges
+ * ab bc ca | of vertices a b c | index of the source triangle (uint32 bits) | 0.  An open or non-manifold mesh still builds (open_edges
+ * counts the edges with other than two faces); the sign near such a defect is whatever the rule below gives with the one-sided sums.
+ * SDFHIP_ERR_ARG: null pointer, n = 0, stride not 3 or 6, a non-finite coordinate, |coordinate| > 1024 after the fit, fill not in
+ * (0, 1024], no triangle left, an options struct the size rules of sdfhip_mesh_options refuse.
+ * build, pinned: fp32, each operation rounded in the order written, dot(x, y) = (x0*y0 + x1*y1) + x2*y2.
+ *   distance of p to a record (Ericson's region test, in this order)
+ *     ab = b-a, ac = c-a, ap = p-a, d1 = dot(ab,ap), d2 = dot(ac,ap);  d1 <= 0 && d2 <= 0: vertex a
+ *     bp = p-b, d3 = dot(ab,bp), d4 = dot(ac,bp);                      d3 >= 0 && d4 <= d3: vertex b
+ *     vc = d1*d4 - d3*d2;            vc <= 0 && d1 >= 0 && d3 <= 0: edge ab, q = a + ab*(d1/(d1-d3))
+ *     cp = p-c, d5 = dot(ab,cp), d6 = dot(ac,cp);                      d6 >= 0 && d5 <= d6: vertex c
+ *     vb = d5*d2 - d1*d6;            vb <= 0 && d2 >= 0 && d6 <= 0: edge ca, q = a + ac*(d2/(d2-d6))
+ *     va = d3*d6 - d5*d4;            va <= 0 && (d4-d3) >= 0 && (d5-d6) >= 0: edge bc, q = b + (c-b)*((d4-d3)/((d4-d3)+(d5-d6)))
+ *     else the face: den = 1/((va+vb)+vc), q = (a + ab*(vb*den)) + ac*(vc*den)
+ *     r = p - q, D = dot(r, r)
+ *   winner    the record with the smallest D by strict <, so a NaN never wins; ties go to the lowest record index; no winner: +inf
+ *   value     s = dot(r, N), N the winner's face, edge or vertex pseudonormal by the region that returned; s < 0 ? -sqrtf(D) : sqrtf(D)
+ *   tree      scene_gen's construct rule (SdfGen/dllmain.cpp:163-190) with this distance: corner k of a node of depth d at pos +
+ *             split(k) * S, S = 2^-d (exact dyadics); byte = FromFloat(value, S) (dllmain.cpp:192-196); a node splits iff
+ *             fabsf(value(centre)) < 2 * S && d < depth
+ *   order     breadth first: node 0 the root (parent -1); a level's child blocks of eight follow in ascending parent index (the order
+ *             sdfhip_scene_edit appends in); a leaf's children is -1
+ * The GPU keeps a candidate list per block of eight siblings and prunes it conservatively (DESIGN.md N8 derives the slack): the bytes
+ * are those of brute force over all records.  depth 0..12.  scene, host_out: either may be NULL, not both; stats may be NULL.
+ * SDFHIP_ERR_ARG: a null mesh or records, n_records = 0, depth outside 0..12, both outputs NULL, more than 2^31 - 1 nodes;
+ * SDFHIP_ERR_NOMEM: out of device memory (nothing leaks, no handle is returned).  Memory comes from the builder's chunk pool
+ * (sdfhip_sdfgen_trim gives it back). */
+typedef struct sdfhip_trimesh_options {
+    uint32_t size;          /* set by sdfhip_trimesh_options_default; grows like sdfhip_mesh_options */
+    int32_t fit;            /* -1 = default (0): coordinates as given; 1: centre the bounding box at 0.5, longest side = fill */
+    float fill;             /* -1 = default (0.8f) */
+} sdfhip_trimesh_options;
+typedef struct sdfhip_trimesh {
+    uint32_t n_records;
+    float *records;         /* n_records x 32 floats */
+    uint32_t n_vertices, n_edges;      /* welded vertices and edges of the triangles kept */
+    uint32_t n_dropped, open_edges;    /* triangles dropped; edges with other than two faces */
+    float scale, offset[3];            /* the fit's s and mid */
+} sdfhip_trimesh;
+typedef struct sdfhip_trimesh_stats {
+    uint32_t nodes, levels, records, pad_;
+    uint64_t candidate_entries;        /* sum of all candidate-list lengths: the work measure */
+    float build_ms;                    /* HIP events around the build's kernels */
+    float scene_ms;                    /* building the handle (fused records, lookup grids), host clock */
+    float total_ms;                    /* host clock, the whole call */
+    uint32_t pad1_;
+} sdfhip_trimesh_stats;
+SDFHIP_API int sdfhip_load_ply_mesh(const char *path, sdfhip_mesh *out);
+SDFHIP_API int sdfhip_load_obj_mesh(const char *path, sdfhip_mesh *out);
+SDFHIP_API void sdfhip_trimesh_options_default(sdfhip_trimesh_options *opt);
+SDFHIP_API int sdfhip_trimesh_prepare(const float *verts, uint32_t n_triangles, uint32_t stride, const sdfhip_trimesh_options *opt,
+                                      sdfhip_trimesh *out);
+SDFHIP_API void sdfhip_trimesh_free(sdfhip_trimesh *mesh);
+SDFHIP_API int sdfhip_trimesh_build(int device, const sdfhip_trimesh *mesh, int32_t depth, sdfhip_scene **scene, sdfhip_octdata *host_out,
+                                    sdfhip_trimesh_stats *stats);
+
 /* ---- one frame over several GPUs, behind one call -----------------------------------------------------------
  * Replaces: Program.Draw's UpdateBuffer(info) + DispatchSized(W, H, 1) (SdfBox/Program.cs:81,94) when the frame is rendered by
  * the GPUs of a node: the host still makes ONE call per frame.  One process; the scene is replicated on every device at

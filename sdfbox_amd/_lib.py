@@ -50,7 +50,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CPoints, Edit, EditStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -195,6 +195,29 @@ else:
                     ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
 
 
+    class TriMeshOptions(ctypes.Structure):
+        """sdfhip_trimesh_options: fit 0 = coordinates as given, 1 = bounding box centred at 0.5 with its longest side `fill` (None = default)."""
+        _fields_ = [("size", ctypes.c_uint32), ("fit", ctypes.c_int32), ("fill", ctypes.c_float)]
+
+        def __init__(self, fit=None, fill=None):
+            super().__init__(ctypes.sizeof(type(self)), -1 if fit is None else int(fit), -1.0 if fill is None else float(fill))
+
+
+    class CTriMesh(ctypes.Structure):
+        _fields_ = [("n_records", ctypes.c_uint32), ("records", ctypes.POINTER(ctypes.c_float)), ("n_vertices", ctypes.c_uint32),
+                    ("n_edges", ctypes.c_uint32), ("n_dropped", ctypes.c_uint32), ("open_edges", ctypes.c_uint32), ("scale", ctypes.c_float),
+                    ("offset", ctypes.c_float * 3)]
+
+
+    class TriMeshStats(ctypes.Structure):
+        _fields_ = [("nodes", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("records", ctypes.c_uint32), ("pad_", ctypes.c_uint32),
+                    ("candidate_entries", ctypes.c_uint64), ("build_ms", ctypes.c_float), ("scene_ms", ctypes.c_float),
+                    ("total_ms", ctypes.c_float), ("pad1_", ctypes.c_uint32)]
+
+
+    assert (ctypes.sizeof(TriMeshOptions), ctypes.sizeof(TriMeshStats)) == (12, 40)
+
+
     class SdfHipError(RuntimeError):
         def __init__(self, code, message):
             super().__init__(f"sdfhip error {code}: {message}")
@@ -270,6 +293,13 @@ _SIG = {
     "sdfhip_mesh_free": (None, [_c.POINTER(CMesh)]),
     "sdfhip_mesh_save_ply": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
     "sdfhip_mesh_save_obj": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
+    "sdfhip_load_ply_mesh": (_c.c_int, [_c.c_char_p, _c.POINTER(CMesh)]),
+    "sdfhip_load_obj_mesh": (_c.c_int, [_c.c_char_p, _c.POINTER(CMesh)]),
+    "sdfhip_trimesh_options_default": (None, [_c.POINTER(TriMeshOptions)]),
+    "sdfhip_trimesh_prepare": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _c.POINTER(TriMeshOptions), _c.POINTER(CTriMesh)]),
+    "sdfhip_trimesh_free": (None, [_c.POINTER(CTriMesh)]),
+    "sdfhip_trimesh_build": (_c.c_int, [_c.c_int, _c.POINTER(CTriMesh), _c.c_int32, _c.POINTER(_vp), _c.POINTER(COctData),
+                                        _c.POINTER(TriMeshStats)]),
     "sdfhip_scene_top_grid": (_c.c_int, [_vp, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_uint64)]),
     "sdfhip_render_bands_device": (_c.c_int, [_vp, _c.POINTER(Info), _c.c_uint32, _c.POINTER(PathTrace), _c.c_uint32,
                                               _c.c_uint32, _c.c_uint32, _c.POINTER(_c.c_uint16), _c.c_uint32,

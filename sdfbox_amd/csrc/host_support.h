@@ -3,7 +3,9 @@
 #pragma once
 #include "scene.h"
 
+#include <chrono>
 #include <thread>
+#include <vector>
 
 // HIP_TRY (scene.h) with a translation unit's prefix in front of the message.  Used through one-line aliases that pass #expr as
 // `text`, so that the message shows the call as it was written: #define M_TRY(expr) HIP_TRY_AS("multi: ", expr, #expr)
@@ -66,5 +68,41 @@ hipError_t tree_to_host(const void *d_structs, const void *d_values, size_t n, A
 // holds none (or SDFHIP_GEN_POOL=0).
 void *pool_take(int device, size_t want, size_t *size);
 void pool_give(int device, void *base, size_t size);
+
+// The builders' device memory (sdfgen_device.hip, trigen.hip).  Bump allocator over a few large hipMalloc chunks.  reset() makes the memory reusable; work on
+// the (single, in-order) stream that still reads the old contents was launched before whatever
+// is launched to overwrite them, so no synchronisation is needed.  The chunks outlive a build: they come from and go back to the
+// per-process pool of device_memory.hip.
+struct Arena {
+    struct Chunk { char *base; size_t size, used; };
+    std::vector<Chunk> chunks;
+    size_t grow;
+    int device = 0;
+    explicit Arena(size_t grow) : grow(grow) { (void)hipGetDevice(&device); }
+    Arena(const Arena &) = delete;
+    Arena &operator=(const Arena &) = delete;
+    void *take(size_t bytes)
+    {
+        bytes = (bytes + 255) & ~(size_t)255;
+        if (bytes == 0) bytes = 256;
+        for (auto &c : chunks)
+            if (c.size - c.used >= bytes) { void *p = c.base + c.used; c.used += bytes; return p; }
+        size_t size = bytes > grow ? bytes : grow;
+        void *p = pool_take(device, size, &size);
+        if (!p) {
+            const auto t0 = std::chrono::steady_clock::now();
+            // (device_alloc_bytes: the pool may be holding what this allocation needs, in chunks of other sizes)
+            if (device_alloc_bytes(&p, size) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (ms > 5.0f && lab_env("SDFHIP_GEN_LEVELS")) fprintf(stderr, "sdfgen: hipMalloc(%zu MB) took %.1f ms\n", size >> 20, ms);
+        }
+        chunks.push_back(Chunk{ (char *)p, size, bytes });
+        grow = grow < ((size_t)1 << 30) ? grow * 2 : grow;
+        return p;
+    }
+    template <class T> T *alloc(size_t n) { return (T *)take(n * sizeof(T)); }
+    void reset() { for (auto &c : chunks) c.used = 0; }
+    ~Arena() { for (auto &c : chunks) pool_give(device, c.base, c.size); }
+};
 
 }  // namespace sdfhip

@@ -42,42 +42,6 @@ using namespace sdfhip;
 
 namespace {
 
-// Bump allocator over a few large hipMalloc chunks.  reset() makes the memory reusable; work on
-// the (single, in-order) stream that still reads the old contents was launched before whatever
-// is launched to overwrite them, so no synchronisation is needed.  The chunks outlive a build: they come from and go back to the
-// per-process pool of device_memory.hip.
-struct Arena {
-    struct Chunk { char *base; size_t size, used; };
-    std::vector<Chunk> chunks;
-    size_t grow;
-    int device = 0;
-    explicit Arena(size_t grow) : grow(grow) { (void)hipGetDevice(&device); }
-    Arena(const Arena &) = delete;
-    Arena &operator=(const Arena &) = delete;
-    void *take(size_t bytes)
-    {
-        bytes = (bytes + 255) & ~(size_t)255;
-        if (bytes == 0) bytes = 256;
-        for (auto &c : chunks)
-            if (c.size - c.used >= bytes) { void *p = c.base + c.used; c.used += bytes; return p; }
-        size_t size = bytes > grow ? bytes : grow;
-        void *p = pool_take(device, size, &size);
-        if (!p) {
-            const auto t0 = std::chrono::steady_clock::now();
-            // (device_alloc_bytes: the pool may be holding what this allocation needs, in chunks of other sizes)
-            if (device_alloc_bytes(&p, size) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            if (ms > 5.0f && lab_env("SDFHIP_GEN_LEVELS")) fprintf(stderr, "sdfgen: hipMalloc(%zu MB) took %.1f ms\n", size >> 20, ms);
-        }
-        chunks.push_back(Chunk{ (char *)p, size, bytes });
-        grow = grow < ((size_t)1 << 30) ? grow * 2 : grow;
-        return p;
-    }
-    template <class T> T *alloc(size_t n) { return (T *)take(n * sizeof(T)); }
-    void reset() { for (auto &c : chunks) c.used = 0; }
-    ~Arena() { for (auto &c : chunks) pool_give(device, c.base, c.size); }
-};
-
 // scratch: arrays only the level itself and k_children read; keep: what the final ordering needs
 bool alloc_level(Arena &scratch, Arena &keep, LevelArrays &L, size_t n)
 {

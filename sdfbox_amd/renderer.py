@@ -3,6 +3,7 @@
 on an MI355X through libsdfhip.so.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -434,6 +435,104 @@ class MultiScene:
     def debug_floats_sent(self, floats):
         _lib.need_lab("MultiScene.debug_floats_sent")
         check(lib.sdfhip_multi_debug_floats_sent(self._h, int(floats)))
+
+
+class TriMesh:
+    """A triangle mesh prepared for the exact signed-distance builder (sdfhip_trimesh_prepare / sdfhip_trimesh_build): per triangle
+    kept a 32-float record -- a b c, face normal, angle-weighted pseudonormals of its edges and vertices, source index."""
+
+    def __init__(self, vertices, stride, fit=None, fill=None):
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3 * stride)
+        opt = _lib.TriMeshOptions(fit, fill)
+        self._raw = _lib.CTriMesh()
+        check(lib.sdfhip_trimesh_prepare(v.ctypes.data, len(v), int(stride), ctypes.byref(opt), ctypes.byref(self._raw)))
+        r = self._raw
+        self.n_vertices, self.n_edges, self.n_dropped, self.open_edges = r.n_vertices, r.n_edges, r.n_dropped, r.open_edges
+        self.scale, self.offset = r.scale, tuple(r.offset)
+
+    @classmethod
+    def FromSoup(cls, triangles, fit=None, fill=None):
+        """triangles: (n, 3, 3) float32 positions, counter-clockwise seen from outside."""
+        return cls(np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 3, 3), 3, fit, fill)
+
+    @classmethod
+    def FromMesh(cls, triangles, fit=None, fill=None):
+        """triangles: (n, 3, 6) float32 {position, normal} as Scene.Mesh returns them; the normals are ignored."""
+        return cls(np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 3, 6), 6, fit, fill)
+
+    @classmethod
+    def LoadPly(cls, path, fit=None, fill=None):
+        return cls.FromMesh(LoadMeshPly(path), fit, fill)
+
+    @classmethod
+    def LoadObj(cls, path, fit=None, fill=None):
+        return cls.FromMesh(LoadMeshObj(path), fit, fill)
+
+    @property
+    def n_records(self):
+        return self._raw.n_records
+
+    @property
+    def records(self):
+        """(n_records, 32) float32: a view of the library's memory, valid until close()."""
+        n = self._raw.n_records
+        return np.ctypeslib.as_array(self._raw.records, shape=(n, 32)) if n else np.zeros((0, 32), np.float32)
+
+    def Build(self, depth, device=0, want_octdata=False, want_scene=True, want_stats=False):
+        """The mesh's exact signed distance field as a Scene on `device` (the tree never leaves HBM), and / or its host arrays."""
+        from .octdata import OctData
+        scene = Scene.__new__(Scene)
+        scene._h = ctypes.c_void_p()
+        scene.device = int(device)
+        raw = _lib.COctData()
+        st = _lib.TriMeshStats()
+        check(lib.sdfhip_trimesh_build(int(device), ctypes.byref(self._raw), int(depth), ctypes.byref(scene._h) if want_scene else None,
+                                       ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        out = []
+        if want_scene:
+            scene._describe()
+            out.append(scene)
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def close(self):
+        if self._raw.records:
+            lib.sdfhip_trimesh_free(ctypes.byref(self._raw))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _load_mesh(fn, path):
+    raw = _lib.CMesh()
+    check(fn(os.fsencode(str(path)), ctypes.byref(raw)))
+    try:
+        n = raw.n_triangles
+        return np.ctypeslib.as_array(raw.verts6, shape=(n, 3, 6)).copy() if n else np.zeros((0, 3, 6), np.float32)
+    finally:
+        lib.sdfhip_mesh_free(ctypes.byref(raw))
+
+
+def LoadMeshPly(path):
+    """sdfhip_load_ply_mesh: a binary little-endian .ply WITH its faces as an (n, 3, 6) float32 soup (polygons fanned)."""
+    return _load_mesh(lib.sdfhip_load_ply_mesh, path)
+
+
+def LoadMeshObj(path):
+    """sdfhip_load_obj_mesh: an .obj WITH its faces as an (n, 3, 6) float32 soup (polygons fanned; normals from the file, else 0)."""
+    return _load_mesh(lib.sdfhip_load_obj_mesh, path)
 
 
 def _as_mesh(triangles):
