@@ -1,6 +1,7 @@
 """Triangle mesh -> exact signed distance, the parts that need no GPU: sdfhip_trimesh_prepare against known pseudonormals and against
 the restatement's own preparation, its refusals, the fit; the restatement (tests/trimesh_restatement.py) against closed-form truth
-it did not make -- the box distance and the sphere -- on its float distances before quantisation; the readers of files with faces."""
+it did not make -- the box distance and the sphere -- on its float distances before quantisation; the readers of files with faces;
+the pruned restatement against the brute-force one on the adversarial soups, and those soups' ties and NaN."""
 import ctypes
 import os
 import struct
@@ -181,6 +182,81 @@ def test_restatement_against_the_sphere(sb):
         assert (np.sign(got[far]) == np.sign(want[far])).all(), depth
         n += len(got)
     assert len(floats) == 5 and n > 5000
+
+
+def truncated(tree, depth):
+    """the depth-`depth` tree out of a deeper one: the same nodes down to that level, whose nodes are leaves"""
+    structs, values, floats = tree
+    n = sum(len(f[0]) for f in floats[:depth + 1])
+    last = n - len(floats[min(depth, len(floats) - 1)][0])
+    S = structs[:n].copy()
+    if depth < len(floats) - 1:
+        S[last:, 1] = -1
+    return S, values[:n]
+
+
+@pytest.mark.parametrize("name", list(tr.ADVERSARIAL))
+def test_pruned_restatement_is_the_brute_force_one(name):
+    """build_pruned (the GPU's candidate lists and their threshold, np.float32) against build (every record at every point) on the
+    adversarial soups, byte for byte, depths 4 and 5 (two_sheets, 2176 records: depth 4); the lists save work"""
+    R = tr.prepare(getattr(tr, name)(), fit=tr.ADVERSARIAL[name])[0]
+    deepest = 4 if name == "two_sheets" else 5
+    brute = tr.build(R, deepest, want_float=True)
+    for depth in range(4, deepest + 1):
+        S, V = truncated(brute, depth)
+        gS, gV, entries = tr.build_pruned(R, depth)
+        assert gS.shape == S.shape and (gS == S).all() and (gV == V).all(), depth
+        blocks = 1 + int((S[:, 1] >= 0).sum())
+        if len(S) > 1:
+            assert len(R) < entries < blocks * len(R), (depth, entries, blocks)
+        else:
+            assert entries == len(R) and (V == 255).all()     # far_away: the root alone, saturated
+    assert (len(S) == 1) == (name == "far_away")
+    if name == "strips_far":
+        assert np.abs(R[:, :9]).max() > 900
+    _cache["brute", name] = (R, brute)
+
+
+def test_two_sheets_tie_with_opposite_signs():
+    """every lattice point on z = 0.5 over the sheets has bit-equal D to a record of sheet B and to its mirror image in sheet A,
+    1088 records on, and the value carries the sign of the lower index (below B: negative)"""
+    R, brute = _cache.get(("brute", "two_sheets")) or (tr.prepare(tr.two_sheets())[0], None)
+    m = len(R) // 2
+    assert m == 1088 and (R[:m, 2] == 0.625).all() and (R[m:, 2] == 0.375).all()
+    x, y = np.meshgrid(0.375 + np.arange(9) / 32.0, 0.4375 + np.arange(5) / 32.0)      # the depth-5 lattice over the sheets
+    p = np.stack([x.ravel(), y.ravel(), np.full(x.size, 0.5)], 1).astype(f32)
+    D, r, region = tr.dist2(R, p)
+    assert not np.isnan(D).any()
+    lower_wave = 0
+    for k in range(len(p)):
+        tie = np.nonzero(D[k] == D[k].min())[0]
+        first = tie[0]
+        assert first < m and first + m in tie and D[k, first] == f32(0.125) ** 2
+        sign = lambda t: tr._dot([r[a][k, t] for a in range(3)], [R[t, tr.REGION_NORMAL[int(region[k, t])] + a] for a in range(3)])
+        assert sign(first) < 0 < sign(first + m)
+        for t in tie[tie < m]:                                 # a record and its image: another chunk of 1024, another wave of 64
+            assert t // 1024 != (t + m) // 1024 and t % 1024 // 64 != (t + m) % 1024 // 64 and t % 256 // 64 != (t + m) % 256 // 64
+        lower_wave += int((first + m) % 1024 // 64 < first % 1024 // 64)
+    assert lower_wave > 0                                      # (the image sits in a lower wave: "the lowest wave wins" is wrong here)
+    assert (tr.values(R, p) == f32(-0.125)).all()
+    assert (tr.from_float(f32(-0.125), f32(2.0 ** -5)) != tr.from_float(f32(0.125), f32(2.0 ** -5)))
+
+
+def test_sliver_has_nan_distances_in_the_tree(sb):
+    """the extra triangle of `sliver` is kept by prepare and its D is NaN at corners of the depth-4 tree; a NaN never wins"""
+    R, brute = _cache.get(("brute", "sliver")) or (None, None)
+    if R is None:
+        R = tr.prepare(tr.sliver())[0]
+        brute = tr.build(R, 5, want_float=True)
+    assert len(R) == 13 and R[12, 30].view(np.uint32) == 12
+    coords, cv, _ = brute[2][4]
+    corners = (coords[:, None, :] + tr.CORNER[None]).reshape(-1, 3).astype(f32) * f32(2.0 ** -4)
+    D = tr.dist2(R[12:], corners)[0][:, 0]
+    bad = np.isnan(D)
+    assert bad.sum() >= 8 and (corners[bad, 0] == 0).all() and (corners[bad, 1] > 0).all()
+    assert np.isfinite(cv.reshape(-1)[bad]).all()              # the cube answers there
+    with sb.TriMesh.FromSoup(tr.sliver()) as m:                # the library's prepare keeps it too
+        assert (m.n_dropped, m.n_records) == (0, 13) and same_bits(m.records[:, :9], R[:, :9])
 
 
 def test_readers_give_back_what_the_writers_wrote(sb, tmp_path):
