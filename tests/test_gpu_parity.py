@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import CAMERAS, GOLDEN, assert_frames_identical, bits_equal, make_camera
+from tree_zoo import _chain_tree, _random_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -165,19 +166,6 @@ def test_camera_edge_cases(sb, oracle_mod, scenes, gpu_scenes):
             assert (st.n_nodes, st.n_samples, st.n_steps, st.n_shadow_rays) == tuple(int(c) for c in cnt), what
             # the build that does not count (the one that is timed) is its own set of kernels
             assert_frames_identical(scene.Draw(cam, W, H, flags_of(sb, variant)), ref, f"{what} / {variant}, not counting")
-
-
-def _chain_tree(depth):
-    """A consistent tree that is `depth` levels deep along the (0,0,0) corner."""
-    rng = np.random.default_rng(depth)
-    n = 1 + 8 * depth
-    s = np.full((n, 2), -1, dtype=np.int32)
-    for lvl in range(depth):
-        node = 0 if lvl == 0 else 1 + 8 * (lvl - 1)       # child 0 of the previous block
-        s[node, 1] = 1 + 8 * lvl
-        s[1 + 8 * lvl: 9 + 8 * lvl, 0] = node
-    v = rng.integers(40, 255, size=(n, 8), dtype=np.uint8)
-    return s, v
 
 
 def test_degenerate_and_deep_trees(sb, oracle_mod):
@@ -1086,34 +1074,6 @@ def test_host_frames_in_page_locked_memory(sb, dragon):
 
 
 # ---- fuzz: random trees, on-grid cameras, axis-aligned rays ---------------------------------
-def _random_tree(rng, max_depth, p_split, max_nodes=60000):
-    """A consistent octree with random splits (DFS pre-order, like SdfGen) and random bytes."""
-    structs = [[-1, -1]]
-
-    def grow(node, depth):
-        if depth >= max_depth or len(structs) + 8 > max_nodes or rng.random() > p_split:
-            return
-        c = len(structs)
-        structs[node][1] = c
-        for _ in range(8):
-            structs.append([node, -1])
-        for k in range(8):
-            grow(c + k, depth + 1)
-
-    grow(0, 0)
-    s = np.array(structs, dtype=np.int32)
-    mode = rng.integers(3)
-    if mode == 0:
-        v = rng.integers(0, 256, size=(len(s), 8), dtype=np.uint8)
-    elif mode == 1:      # mostly flat cells (exercises the flat fast path next to non-flat lanes)
-        v = np.repeat(rng.integers(0, 256, size=(len(s), 1), dtype=np.uint8), 8, axis=1)
-        noisy = rng.random(len(s)) < 0.2
-        v[noisy] = rng.integers(0, 256, size=(int(noisy.sum()), 8), dtype=np.uint8)
-    else:                # a crude distance-like field: larger values near the cube faces
-        v = rng.integers(60, 200, size=(len(s), 8), dtype=np.uint8)
-    return s, v
-
-
 def test_nan_coordinates_select_the_low_cells(sb, oracle_mod):
     # A NaN coordinate fails every comparison of inside() (up to the root) and saturates to 0 in the descent
     # (Compute.hlsl:93-106): the shader lands in the cell at the LOW end of that axis.  On a tree whose corners hold
