@@ -190,6 +190,18 @@ public:
         sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Pruning (sdfhip_scene_prune): the blocks of eight that say nothing their parent does not already say -- within `tolerance` bytes
+    // (0..255) of what the parent's bytes interpolate to, or below max_depth (-1 = no cut, else 0..12) -- are removed, and the
+    // pruned model replaces the loaded one as Edit's result does.  host_out (may be null): the pruned tree's host arrays
+    void Prune(int tolerance = 0, int max_depth = -1, sdfhip_prune_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Prune: no model loaded");
+        const sdfhip_prune_options opt = { (uint32_t)sizeof(sdfhip_prune_options), tolerance, max_depth };
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_prune(scene, &opt, &fresh, host_out, stats));
+        sdfhip_scene_free(scene);
+        scene = fresh;
+    }
     // Point and ray queries (sdfhip_scene_sample / _raycast / _pick; nothing in the reference corresponds): what the loaded model
     // answers without drawing a frame, with the shader's own arithmetic.  Sample: distance, cell and gradient at points (xyz: 3 floats
     // per point); Raycast: the primary march of Compute.hlsl:194-203 for arbitrary rays; Pick: that march for pixels {x, y} of the

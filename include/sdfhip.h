@@ -465,7 +465,7 @@ SDFHIP_API int sdfhip_deinterleave_sparse2_device(int device, const void *const 
  *               (carve) or min(p, q(g, S)) (add), p its byte before the edit
  *   refinement: a leaf above max_depth whose centre has |s| < 2 S (the builder's band, Model.cs:44) and where the brush wins over
  *               the trilinear value of its corners (carve: g > v, add: g < v) gets 8 children, whose values before the edit are
- *               the parent's, interpolated; they are edited by the same rules, recursively.  Nothing is pruned.
+ *               the parent's, interpolated; they are edited by the same rules, recursively.  Nothing is pruned (sdfhip_scene_prune does).
  *   node order: original nodes keep their indices; new blocks of 8 are appended in the order (depth of the block, parent index).
  * max_depth: -1 = the input's depth, else 0..12 (deeper than the input lets brushes refine past it).  host_out (may be NULL): the
  * result's host arrays, as sdfhip_sdfgen_scene's `out` (release with sdfhip_octdata_free).  stats (may be NULL).
@@ -490,6 +490,48 @@ typedef struct sdfhip_edit_stats {
 } sdfhip_edit_stats;
 SDFHIP_API int sdfhip_scene_edit(sdfhip_scene *scene, const sdfhip_edit *edits, uint32_t n_edits, int32_t max_depth, sdfhip_scene **out,
                                  sdfhip_octdata *host_out, sdfhip_edit_stats *stats);
+
+/* ---- pruning: collapse the blocks of a resident scene that their parent already describes ------------
+ * Replaces: nothing in the reference's code -- a tree there is immutable once built, and sdfhip_scene_edit only ever grows one.
+ * sdfhip_scene_prune removes the redundant blocks of eight of the tree of `scene` on its device and returns the result as a NEW handle
+ * `*out` on the same device: the input is untouched (frames in flight on it included) and either handle may be freed first.  The
+ * tree leaves HBM only for host_out.  The rule, pinned (fp32, each operation rounded on its own in the order written, as the edit's):
+ *   inherited byte   for an internal node P of depth d, S = 2^-d, bytes b[0..7]: f[j] = ((b[j] / 255.0f) - 0.25f) * S * 2.0f; child
+ *                    i's corner k sits at t_a = ((i >> a & 1) + (k >> a & 1)) * 0.5f per axis a; v = trilerp(f, t_x, t_y, t_z) with
+ *                    lerp(a, b, t) = a + (b - a) * t along x, then y, then z; q(i, k) = floorf(saturate(v / 2 / (S * 0.5f) + 0.25f) * 255)
+ *                    -- exactly the byte sdfhip_scene_edit gives a new child before the brush touches it
+ *   redundant block  the eight children of P are redundant iff (1) every child is a leaf, or has become one by this rule, and
+ *                    (2) the children's depth d + 1 exceeds max_depth (when max_depth >= 0), or every one of the 64 bytes has
+ *                    |byte(i, k) - q(i, k)| <= tolerance, compared as integers
+ *   cascade          a redundant block is removed and P becomes a leaf (children -1) with its own bytes; decided from the deepest
+ *                    level up, so one call collapses as many levels as collapse
+ *   node order       survivors keep their relative order: a survivor's new index is the number of survivors with a lower old index;
+ *                    parent and children are remapped, no surviving byte changes, blocks of eight stay contiguous (siblings live or
+ *                    die together).  The result depends on the input arrays and the two options alone, never on which wave finished
+ *                    first.
+ * opt: NULL = defaults.  tolerance: 0..255, -1 = the default, 0.  max_depth: -1 = no cut, else 0..12.  The struct grows like
+ * sdfhip_mesh_options: the caller sets size = sizeof(sdfhip_prune_options); a larger, newer struct is accepted when the fields this
+ * library does not know are all -1.  Tolerance 0 without a cut on a tree with nothing redundant is a clone; tolerance 255, or
+ * max_depth 0, gives the root alone.  host_out (may be NULL): the result's host arrays (release with sdfhip_octdata_free).  stats
+ * (may be NULL).
+ * SDFHIP_ERR_ARG: a null scene or output, tolerance outside -1..255, max_depth outside -1..12, an options struct the size rules
+ * refuse; SDFHIP_ERR_BAD_TREE: the tree is not consistent (stack_kernel_ok == 0 in sdfhip_scene_info) or deeper than 12 levels, as
+ * sdfhip_scene_edit refuses it; SDFHIP_ERR_NOMEM: out of device memory (the input stays valid, nothing leaks).
+ * Work is proportional to the tree: every record is read, every survivor written; the new handle builds its lookup grids anew. */
+typedef struct sdfhip_prune_options {
+    uint32_t size;          /* sizeof(sdfhip_prune_options) of the caller's header */
+    int32_t tolerance;      /* 0..255; -1 = default (0) */
+    int32_t max_depth;      /* -1 = no cut; 0..12: every block whose children are deeper is removed */
+} sdfhip_prune_options;
+typedef struct sdfhip_prune_stats {
+    uint32_t nodes_in, nodes_out;
+    uint32_t blocks_removed, depth_out;
+    float kernel_ms;         /* HIP events around the prune's kernels */
+    float scene_ms;          /* building the new handle (fused records, lookup grids), host clock */
+    float total_ms;          /* host clock, the whole call */
+} sdfhip_prune_stats;
+SDFHIP_API int sdfhip_scene_prune(sdfhip_scene *scene, const sdfhip_prune_options *opt, sdfhip_scene **out, sdfhip_octdata *host_out,
+                                  sdfhip_prune_stats *stats);
 
 /* ---- point and ray queries: what a resident scene answers without drawing a frame -------------------
  * Replaces: nothing in the reference's code -- its only consumer of the tree is Compute.hlsl; a host that wants the distance at a

@@ -50,7 +50,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -156,6 +156,22 @@ else:
         _fields_ = [("nodes_in", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("nodes_visited", ctypes.c_uint32),
                     ("nodes_changed", ctypes.c_uint32), ("blocks_added", ctypes.c_uint32), ("depth_out", ctypes.c_uint32),
                     ("edit_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
+    class PruneOptions(ctypes.Structure):
+        """sdfhip_prune_options: tolerance 0..255 (None = the default, 0); max_depth None = no cut, else 0..12."""
+        _fields_ = [("size", ctypes.c_uint32), ("tolerance", ctypes.c_int32), ("max_depth", ctypes.c_int32)]
+
+        def __init__(self, tolerance=None, max_depth=None):
+            super().__init__(ctypes.sizeof(type(self)), -1 if tolerance is None else int(tolerance), -1 if max_depth is None else int(max_depth))
+
+
+    class PruneStats(ctypes.Structure):
+        _fields_ = [("nodes_in", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("blocks_removed", ctypes.c_uint32),
+                    ("depth_out", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(PruneOptions), ctypes.sizeof(PruneStats)) == (12, 28)
 
 
     class Probe(ctypes.Structure):
@@ -282,6 +298,7 @@ _SIG = {
     "sdfhip_camera_mouse_wheel": (_c.c_float, [_c.c_float, _c.c_float]),
     "sdfhip_scene_edit": (_c.c_int, [_vp, _c.POINTER(Edit), _c.c_uint32, _c.c_int32, _c.POINTER(_vp), _c.POINTER(COctData),
                                      _c.POINTER(EditStats)]),
+    "sdfhip_scene_prune": (_c.c_int, [_vp, _c.POINTER(PruneOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PruneStats)]),
     "sdfhip_scene_sample": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
     "sdfhip_scene_sample_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),

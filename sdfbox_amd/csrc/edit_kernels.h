@@ -6,6 +6,7 @@
 #pragma once
 #include "raymarch_device.h"
 #include "sdf_bytes.h"
+#include "sdf_interp.h"      // edit_lerp, trilerp
 
 namespace sdfhip {
 
@@ -32,17 +33,6 @@ __device__ __forceinline__ float brush_distance(const EditBrush &B, float px, fl
     const float qx = fabsf(dx) - B.a, qy = fabsf(dy) - B.b, qz = fabsf(dz) - B.c;
     const float ox = fmaxf(qx, 0.0f), oy = fmaxf(qy, 0.0f), oz = fmaxf(qz, 0.0f);
     return sqrtf((ox * ox + oy * oy) + oz * oz) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.0f);
-}
-
-__device__ __forceinline__ float edit_lerp(float a, float b, float t) { return a + (b - a) * t; }
-
-// trilinear interpolation of corner values c[x + 2y + 4z] at (tx, ty, tz): along x, then y, then z
-__device__ __forceinline__ float trilerp(const float c[8], float tx, float ty, float tz)
-{
-    const float e00 = edit_lerp(c[0], c[1], tx), e10 = edit_lerp(c[2], c[3], tx);
-    const float e01 = edit_lerp(c[4], c[5], tx), e11 = edit_lerp(c[6], c[7], tx);
-    const float f0 = edit_lerp(e00, e10, ty), f1 = edit_lerp(e01, e11, ty);
-    return edit_lerp(f0, f1, tz);
 }
 
 // The edit of one node: pre-edit corner values pre[8] and bytes p (8 x 8 bits) in, edited bytes out; whether the brush refines it

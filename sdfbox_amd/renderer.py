@@ -139,6 +139,28 @@ class Scene:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
 
+    def Prune(self, tolerance=0, max_depth=None, want_octdata=False, want_stats=False):
+        """Pruning (sdfhip_scene_prune): the blocks of eight whose bytes are, within `tolerance` (0..255), what their parent's bytes
+        interpolate to -- what Edit gave them before a brush touched them -- are removed, bottom-up, and with max_depth (None = no
+        cut, else 0..12) every block below that depth; the result is a NEW Scene, this one is left as it was.  want_octdata: also
+        the result's host arrays; want_stats: a PruneStats."""
+        from .octdata import OctData
+        opt = _lib.PruneOptions(tolerance, max_depth)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = self.device
+        raw = _lib.COctData()
+        st = _lib.PruneStats()
+        check(lib.sdfhip_scene_prune(self._h, ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None,
+                                     ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
     # -- point and ray queries (sdfhip_scene_sample / _raycast / _pick): answers without a frame ---------------------------------
     def Sample(self, points):
         """Distance, cell and gradient at points (n, 3) float32, with the shader's own arithmetic: a structured array of n records
