@@ -8,8 +8,8 @@
 //                     their bytes edited in place, internal ones push their children, leaves the brush refines are collected
 //   k_edit_new        the new nodes of the level (blocks emitted under the level above's splits): interpolated pre-edit values,
 //                     the edit, the split rule
-//   k_edit_scan_*     the splits' ranks by index, from a bitmap over the node indices (only the words between the lowest and the
-//   k_edit_emit       highest split are scanned) -> blocks appended at the end in the order (depth, parent index)
+//   k_rank_scan_*     the splits' ranks by index, from a bitmap over the node indices (scan_device.h; only the words between the
+//   k_edit_emit       lowest and the highest split are scanned) -> blocks appended at the end in the order (depth, parent index)
 // One host synchronisation per level that has work, per edit: the counts of the next level size its launches and buffers.
 // Then the arrays go to scene_from_arrays (grids, fused records) as the point-cloud builder's do.
 #include "edit_kernels.h"
@@ -29,42 +29,8 @@ using namespace sdfhip;
 
 namespace {
 
-constexpr int EDIT_MAX_DEPTH = 12;          // LM: the deepest tree the grids and the cursor-stack kernels take
-constexpr int EDIT_LEVELS = 16;             // counters per edit (levels 0 .. EDIT_MAX_DEPTH)
+constexpr int EDIT_LEVELS = 16;             // counters per edit (levels 0 .. TREE_MAX_DEPTH)
 constexpr float HALF_SQRT3 = 0.866025404f;  // SdfGen's HalfSqrt3
-
-struct NoMem {};
-
-// The edit's device memory: grown on demand, freed at the end (the arrays the scene is made from included: it keeps its own copy)
-struct Workspace {
-    std::vector<void *> owned;
-    int fail_after = -1;                    // laboratory library: SDFHIP_EDIT_FAIL_ALLOC=k fails the k-th allocation (0 = the first)
-    ~Workspace() { for (void *p : owned) (void)hipFree(p); }
-    void *get(size_t bytes)
-    {
-        void *p = nullptr;
-        if (fail_after == 0) throw NoMem{};
-        if (fail_after > 0) fail_after--;
-        const hipError_t e = device_alloc_bytes(&p, bytes ? bytes : 1);
-        if (e != hipSuccess) { (void)hipGetLastError(); throw NoMem{}; }
-        owned.push_back(p);
-        return p;
-    }
-    void drop(void *p)
-    {
-        for (auto &q : owned)
-            if (q == p) { (void)hipFree(q); q = owned.back(); owned.pop_back(); return; }
-    }
-    // a buffer of at least `need` elements (contents not kept)
-    template <class T> void ensure(T *&p, size_t &cap, size_t need)
-    {
-        if (need <= cap) return;
-        if (p) drop(p);
-        p = nullptr;
-        cap = need + need / 2;
-        p = static_cast<T *>(get(cap * sizeof(T)));
-    }
-};
 
 int check_edit(const sdfhip_edit &e, uint32_t i)
 {
@@ -87,27 +53,21 @@ try {
     const auto t0 = std::chrono::steady_clock::now();
     if (!scene || !out || (n_edits && !edits)) return fail(SDFHIP_ERR_ARG, "scene_edit: null argument");
     *out = nullptr;
-    if (max_depth < -1 || max_depth > EDIT_MAX_DEPTH)
-        return fail(SDFHIP_ERR_ARG, "scene_edit: max_depth %d is neither -1 nor 0..%d", max_depth, EDIT_MAX_DEPTH);
+    if (max_depth < -1 || max_depth > TREE_MAX_DEPTH)
+        return fail(SDFHIP_ERR_ARG, "scene_edit: max_depth %d is neither -1 nor 0..%d", max_depth, TREE_MAX_DEPTH);
     for (uint32_t i = 0; i < n_edits; i++)
         if (const int rc = check_edit(edits[i], i)) return rc;
-    if (!scene->stack_ok || scene->depth > (uint32_t)EDIT_MAX_DEPTH)
-        return fail(SDFHIP_ERR_BAD_TREE, "scene_edit: the input tree is not consistent (or deeper than %d levels): no edit", EDIT_MAX_DEPTH);
+    if (!scene->stack_ok || scene->depth > (uint32_t)TREE_MAX_DEPTH)
+        return fail(SDFHIP_ERR_BAD_TREE, "scene_edit: the input tree is not consistent (or deeper than %d levels): no edit", TREE_MAX_DEPTH);
     const int maxd = max_depth < 0 ? (int)scene->depth : max_depth;
 
     DeviceGuard g(scene->device);
     if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_edit: hipSetDevice(%d) failed", scene->device);
-    Workspace ws;
-    if (const char *e = lab_env("SDFHIP_EDIT_FAIL_ALLOC")) ws.fail_after = atoi(e);
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Release {
-        hipStream_t &st; hipEvent_t &a, &b;
-        ~Release() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } release{ st, ev0, ev1 };
-    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
+    DeviceBuffers ws("SDFHIP_EDIT_FAIL_ALLOC");
+    CallStream<2> cs;                       // (after `ws`: drained before the buffers are freed)
+    if (const int rc = cs.open("")) return rc;
+    const hipStream_t st = cs.st;
+    const hipEvent_t ev0 = cs.ev[0], ev1 = cs.ev[1];
 
     uint64_t n_cur = scene->n;
     uint32_t depth_out = scene->depth;
@@ -117,21 +77,17 @@ try {
     try {
         // the arrays: the input's records, unfused, with room to grow
         cap_nodes = (size_t)n_cur + (n_cur >> 4) + 4096;
-        dS = static_cast<int2 *>(ws.get(cap_nodes * sizeof(int2)));
-        dV = static_cast<uint2 *>(ws.get(cap_nodes * sizeof(uint2)));
+        dS = ws.get<int2>(cap_nodes);
+        dV = ws.get<uint2>(cap_nodes);
         EditEntry *fr_cur = nullptr, *fr_next = nullptr;
         EditSplit *splits = nullptr, *par_cur = nullptr, *par_next = nullptr;
         uint32_t *bitmap = nullptr, *pre = nullptr, *chunk = nullptr;
         size_t c_fr_cur = 0, c_fr_next = 0, c_splits = 0, c_par_cur = 0, c_par_next = 0, c_bitmap = 0, c_pre = 0, c_chunk = 0;
-        EditCounters *cnt = static_cast<EditCounters *>(ws.get(EDIT_LEVELS * sizeof(EditCounters)));
+        EditCounters *cnt = ws.get<EditCounters>(EDIT_LEVELS);
 
         HIP_TRY(hipEventRecord(ev0, st));
-        {
-            const uint32_t blocks_u = (uint32_t)std::min<uint64_t>((n_cur + 255) / 256, 8192);
-            hipLaunchKernelGGL(k_edit_unfuse, dim3(blocks_u), dim3(256), 0, st, scene->nodes, dS, dV, (uint32_t)n_cur);
-            HIP_TRY(hipGetLastError());
-        }
-        const auto grid_of = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)); };
+        hipLaunchKernelGGL(k_edit_unfuse, grid_stride_blocks(n_cur, 8192), dim3(256), 0, st, scene->nodes, dS, dV, (uint32_t)n_cur);
+        HIP_TRY(hipGetLastError());
         for (uint32_t ei = 0; ei < n_edits; ei++) {
             const sdfhip_edit &E = edits[ei];
             EditBrush B;
@@ -158,10 +114,10 @@ try {
                     HIP_TRY(hipMemsetAsync(bitmap, 0, c_bitmap * sizeof(uint32_t), st));
                 }
                 if (n_orig)
-                    hipLaunchKernelGGL(k_edit_original, grid_of(n_orig), dim3(256), 0, st, B, fr_cur, (uint32_t)n_orig, d, S, dS, dV, fr_next,
+                    hipLaunchKernelGGL(k_edit_original, grid_stride_blocks(n_orig), dim3(256), 0, st, B, fr_cur, (uint32_t)n_orig, d, S, dS, dV, fr_next,
                                        splits, bitmap, cnt + d);
                 if (n_new)
-                    hipLaunchKernelGGL(k_edit_new, grid_of(n_new), dim3(256), 0, st, B, par_cur, (uint32_t)first_new, (uint32_t)n_new, d, S,
+                    hipLaunchKernelGGL(k_edit_new, grid_stride_blocks(n_new), dim3(256), 0, st, B, par_cur, (uint32_t)first_new, (uint32_t)n_new, d, S,
                                        dS, dV, splits, bitmap, cnt + d);
                 HIP_TRY(hipGetLastError());
                 EditCounters c;
@@ -175,8 +131,8 @@ try {
                         return fail(SDFHIP_ERR_ARG, "scene_edit: the result would have more than 2^31 - 1 nodes");
                     if (n_cur + 8ull * c.n_split > cap_nodes) {                    // grow the arrays, keeping what they hold
                         const size_t cap = (size_t)(n_cur + 8ull * c.n_split) + (size_t)(n_cur >> 2);
-                        int2 *nS = static_cast<int2 *>(ws.get(cap * sizeof(int2)));
-                        uint2 *nV = static_cast<uint2 *>(ws.get(cap * sizeof(uint2)));
+                        int2 *nS = ws.get<int2>(cap);
+                        uint2 *nV = ws.get<uint2>(cap);
                         HIP_TRY(hipMemcpyAsync(nS, dS, n_cur * sizeof(int2), hipMemcpyDeviceToDevice, st));
                         HIP_TRY(hipMemcpyAsync(nV, dV, n_cur * sizeof(uint2), hipMemcpyDeviceToDevice, st));
                         HIP_TRY(hipStreamSynchronize(st));
@@ -187,9 +143,9 @@ try {
                     ws.ensure(pre, c_pre, m);
                     ws.ensure(chunk, c_chunk, nchunk);
                     ws.ensure(par_next, c_par_next, c.n_split);
-                    hipLaunchKernelGGL(k_edit_scan_words, dim3(nchunk), dim3(256), 0, st, bitmap, w0, m, pre, chunk);
-                    hipLaunchKernelGGL(k_edit_scan_chunks, dim3(1), dim3(1024), 0, st, chunk, nchunk);
-                    hipLaunchKernelGGL(k_edit_emit, grid_of(c.n_split), dim3(256), 0, st, splits, c.n_split, bitmap, w0, pre, chunk,
+                    hipLaunchKernelGGL(k_rank_scan_words<EditWindowWords>, dim3(nchunk), dim3(256), 0, st, EditWindowWords{ bitmap, w0 }, m, pre, chunk);
+                    hipLaunchKernelGGL(k_rank_scan_chunks<false>, dim3(1), dim3(1024), 0, st, chunk, nchunk);
+                    hipLaunchKernelGGL(k_edit_emit, grid_stride_blocks(c.n_split), dim3(256), 0, st, splits, c.n_split, bitmap, w0, pre, chunk,
                                        (uint32_t)n_cur, dS, par_next);
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipMemsetAsync(bitmap + w0, 0, (size_t)m * sizeof(uint32_t), st));
@@ -211,21 +167,8 @@ try {
     float edit_ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&edit_ms, ev0, ev1));
 
-    const auto t1 = std::chrono::steady_clock::now();
-    sdfhip_scene *res = nullptr;
-    const int rc = scene_from_arrays(scene->device, reinterpret_cast<const int32_t *>(dS), reinterpret_cast<const uint8_t *>(dV),
-                                     (uint32_t)n_cur, true, nullptr, &res, (int)depth_out);
-    if (rc != SDFHIP_OK) return rc;
-    const float scene_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    if (host_out) {
-        bool no_host_memory = false;
-        const hipError_t e = tree_to_host(dS, dV, n_cur, malloc, host_out, &no_host_memory);
-        if (e != hipSuccess) {
-            (void)sdfhip_scene_free(res);
-            return no_host_memory ? fail(SDFHIP_ERR_NOMEM, "scene_edit: out of host memory for host_out")
-                                  : fail(SDFHIP_ERR_DEVICE, "scene_edit: copying the tree to the host failed: %s", hipGetErrorString(e));
-        }
-    }
+    float scene_ms = 0.0f;
+    if (const int rc = finish_tree("scene_edit", scene->device, dS, dV, (uint32_t)n_cur, (int)depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_in = scene->n; stats->nodes_out = (uint32_t)n_cur;
         stats->nodes_visited = (uint32_t)std::min<uint64_t>(visited, 0xFFFFFFFFu);
@@ -234,7 +177,6 @@ try {
         stats->edit_ms = edit_ms; stats->scene_ms = scene_ms;
         stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    *out = res;
     return SDFHIP_OK;
 }
 SDFHIP_ABI_CATCH(sdfhip_scene_edit)

@@ -7,6 +7,7 @@
 #include "raymarch_device.h"
 #include "sdf_bytes.h"
 #include "sdf_interp.h"      // edit_lerp, trilerp
+#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap
 
 namespace sdfhip {
 
@@ -193,48 +194,13 @@ __global__ __launch_bounds__(256) void k_edit_new(EditBrush B, const EditSplit *
     if (visited) atomicAdd(&cnt->visited, visited);
 }
 
-// The prefix counts of the split bitmap's words w0 .. w0 + m - 1: per word, the set bits of the words before it in its chunk of
-// 1024 (pre[]), and per chunk its total (chunk[])
-__global__ __launch_bounds__(256) void k_edit_scan_words(const uint32_t *__restrict__ bitmap, uint32_t w0, uint32_t m,
-                                                         uint32_t *__restrict__ pre, uint32_t *__restrict__ chunk)
-{
-    __shared__ uint32_t part[256];
-    const uint32_t t = threadIdx.x, first = blockIdx.x * 1024u + 4u * t;
-    uint32_t c[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { c[k] = first + k < m ? (uint32_t)__popc(bitmap[w0 + first + k]) : 0u; sum += c[k]; }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {          // inclusive scan of the threads' sums (Hillis-Steele)
-        const uint32_t v = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (first + k < m) pre[first + k] = run; run += c[k]; }
-    if (t == 255) chunk[blockIdx.x] = part[255];
-}
-
-// ... the chunks' totals -> exclusive prefix, in one workgroup (at most 65 536 chunks: 2^31 nodes)
-__global__ __launch_bounds__(1024) void k_edit_scan_chunks(uint32_t *__restrict__ chunk, uint32_t nchunk)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
-    uint32_t sum = 0;
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = run; run += v; }
-}
+// The split bitmap's words w0 .. w0 + m - 1 to k_rank_scan_words (scan_device.h): only the words between the level's lowest and
+// highest split are ranked, so word i of the scan is word w0 + i of the bitmap
+struct EditWindowWords {
+    const uint32_t *bitmap;
+    uint32_t w0;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return bitmap[w0 + i]; }
+};
 
 // The level's splits, in any order -> their blocks, in the order of their indices: block rank r = the number of splits of this
 // level with a lower index; the block starts at first + 8 r, its parent's children field points there, and the parent's entry
@@ -246,7 +212,7 @@ __global__ __launch_bounds__(256) void k_edit_emit(const EditSplit *__restrict__
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const EditSplit e = splits[i];
         const uint32_t w = (e.idx >> 5) - w0;
-        const uint32_t r = chunk[w >> 10] + pre[w] + (uint32_t)__popc(bitmap[e.idx >> 5] & ((1u << (e.idx & 31u)) - 1u));
+        const uint32_t r = rank_in_bitmap(chunk, pre, w, bitmap[e.idx >> 5], e.idx & 31u);
         Sarr[e.idx].y = (int32_t)(first + 8u * r);
         parents_next[r] = e;
     }

@@ -21,6 +21,16 @@ int fail(int code, const char *fmt, ...)
 }
 void clear_error() { g_err[0] = 0; }
 
+int check_options_size(const char *what, const void *opt, uint32_t known_bytes, const char *hint)
+{
+    const uint32_t size = *static_cast<const uint32_t *>(opt);
+    if (size < known_bytes || size % 4u || size > 4096u) return fail(SDFHIP_ERR_ARG, "%s: options of %u bytes (%s)", what, size, hint);
+    const int32_t *words = static_cast<const int32_t *>(opt);
+    for (uint32_t k = known_bytes / 4; k < size / 4; k++)
+        if (words[k] != -1) return fail(SDFHIP_ERR_ARG, "%s: options of %u bytes with a field this library does not know set", what, size);
+    return SDFHIP_OK;
+}
+
 // The translation behind SDFHIP_ABI_CATCH*: called inside a catch (...) handler, rethrows to learn the type.  fail() formats
 // into a thread-local array, so nothing here allocates (the usual reason to be here is that allocation has just failed).
 int abi_caught(const char *entry) noexcept

@@ -1,8 +1,11 @@
-// What the host side of libsdfhip.so shares beyond the scene handle.  Not one of the renderer's measured sources (bench_report.py
+// What the host side of libsdfhip.so shares beyond the scene handle: the HIP_TRY prefix form, growable buffers, the builders' arenas,
+// and the call frame of the tree rewriters (edit.hip, prune.hip, trigen.hip: NoMem, AllocFault, DeviceBuffers, CallStream,
+// finish_tree).  Not one of the renderer's measured sources (bench_report.py
 // hashes scene.h, which this header includes and which must never include it): a helper a new translation unit needs goes here.
 #pragma once
 #include "scene.h"
 
+#include <algorithm>
 #include <chrono>
 #include <thread>
 #include <vector>
@@ -104,5 +107,116 @@ struct Arena {
     void reset() { for (auto &c : chunks) c.used = 0; }
     ~Arena() { for (auto &c : chunks) pool_give(device, c.base, c.size); }
 };
+
+// ---- the call frame of the calls that turn a tree on the device into a new scene (edit.hip, prune.hip, trigen.hip) ---------------
+
+constexpr int TREE_MAX_DEPTH = 12;          // LM: the deepest tree the grids and the cursor-stack kernels take
+
+// blocks of 256 threads for a grid-stride loop over `threads` items
+inline dim3 grid_stride_blocks(uint64_t threads, uint32_t cap = 4096) { return dim3((uint32_t)std::min<uint64_t>((threads + 255) / 256, cap)); }
+
+// Thrown by a call's allocator; the entry point catches it and words its SDFHIP_ERR_NOMEM.
+struct NoMem {};
+
+// laboratory library: VARIABLE=k fails the call's k-th allocation (0 = the first), once.  The product reads nothing (lab_env).
+struct AllocFault {
+    int left = -1;
+    explicit AllocFault(const char *variable) { if (const char *e = lab_env(variable)) left = atoi(e); }
+    bool next()                                     // is this allocation the one to fail?
+    {
+        if (left == 0) { left = -1; return true; }
+        if (left > 0) left--;
+        return false;
+    }
+};
+
+// A call's device memory: grown on demand, freed at the end (the arrays the scene is made from included: it keeps its own copy)
+struct DeviceBuffers {
+    std::vector<void *> owned;
+    AllocFault fault;
+    explicit DeviceBuffers(const char *fault_variable) : fault(fault_variable) {}
+    DeviceBuffers(const DeviceBuffers &) = delete;
+    DeviceBuffers &operator=(const DeviceBuffers &) = delete;
+    ~DeviceBuffers() { for (void *p : owned) (void)hipFree(p); }
+    template <class T> T *get(size_t count)
+    {
+        void *p = nullptr;
+        if (fault.next()) throw NoMem{};
+        const hipError_t e = device_alloc_bytes(&p, count ? count * sizeof(T) : 1);
+        if (e != hipSuccess) { (void)hipGetLastError(); throw NoMem{}; }
+        owned.push_back(p);
+        return static_cast<T *>(p);
+    }
+    void drop(void *p)
+    {
+        for (auto &q : owned)
+            if (q == p) { (void)hipFree(q); q = owned.back(); owned.pop_back(); return; }
+    }
+    // a buffer of at least `need` elements (contents not kept)
+    template <class T> void ensure(T *&p, size_t &cap, size_t need)
+    {
+        if (need <= cap) return;
+        if (p) drop(p);
+        p = nullptr;
+        cap = need + need / 2;
+        p = get<T>(cap);
+    }
+};
+
+// A call's own non-blocking stream and N timing events.  The destructor waits for the stream before it destroys anything, so
+// DECLARE IT AFTER the call's DeviceBuffers / arenas: locals die in reverse order, and the stream must be drained before the memory
+// its kernels use is freed (or goes back to the pool) on whatever path the call returns.
+template <int N> struct CallStream {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[N] = {};
+    CallStream() = default;
+    CallStream(const CallStream &) = delete;
+    CallStream &operator=(const CallStream &) = delete;
+    // what: the translation unit's HIP_TRY_AS prefix ("" for plain HIP_TRY)
+    int open(const char *what)
+    {
+        const auto tried = [what](hipError_t e, const char *text) {
+            if (e == hipSuccess) return (int)SDFHIP_OK;
+            (void)hipGetLastError();
+            return fail(SDFHIP_ERR_DEVICE, "%s%s failed: %s", what, text, hipGetErrorString(e));
+        };
+        if (const int rc = tried(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags(&st, hipStreamNonBlocking)")) return rc;
+        for (int k = 0; k < N; k++)
+            if (const int rc = tried(hipEventCreate(&ev[k]), "hipEventCreate(&ev[k])")) return rc;
+        return SDFHIP_OK;
+    }
+    ~CallStream()
+    {
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (int k = 0; k < N; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+    }
+};
+
+// The rewriters' shared tail: the finished arrays (n nodes, `depth` levels deep by construction) as a scene handle when `scene` is
+// given, and as host arrays (malloc) when `host_out` is.  If the copy to the host fails the new scene is freed and *scene stays
+// as it was.  *scene_ms: the host's time for the handle.
+inline int finish_tree(const char *what, int device, const int2 *dS, const uint2 *dV, uint32_t n, int depth, sdfhip_scene **scene,
+                       sdfhip_octdata *host_out, float *scene_ms)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    sdfhip_scene *res = nullptr;
+    if (scene) {
+        const int rc = scene_from_arrays(device, reinterpret_cast<const int32_t *>(dS), reinterpret_cast<const uint8_t *>(dV), n, true, nullptr,
+                                         &res, depth);
+        if (rc != SDFHIP_OK) return rc;
+    }
+    *scene_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (host_out) {
+        bool no_host_memory = false;
+        const hipError_t e = tree_to_host(dS, dV, n, malloc, host_out, &no_host_memory);
+        if (e != hipSuccess) {
+            if (res) (void)sdfhip_scene_free(res);
+            return no_host_memory ? fail(SDFHIP_ERR_NOMEM, "%s: out of host memory for host_out", what)
+                                  : fail(SDFHIP_ERR_DEVICE, "%s: copying the tree to the host failed: %s", what, hipGetErrorString(e));
+        }
+    }
+    if (scene) *scene = res;
+    return SDFHIP_OK;
+}
 
 }  // namespace sdfhip

@@ -46,18 +46,11 @@ Temp g_temp[MAX_DEVICES];
 // DESIGN.md N7); SDFHIP_MESH_FAIL_ALLOC=k fails the call's k-th allocation (0 = the first)
 struct Knobs {
     bool nt = false, wide = true;
-    int fail_after = -1;
+    AllocFault alloc{ "SDFHIP_MESH_FAIL_ALLOC" };
     Knobs()
     {
         if (const char *e = lab_env("SDFHIP_MESH_STORE")) nt = strcmp(e, "nt") == 0;
         if (const char *e = lab_env("SDFHIP_MESH_VEC")) wide = strcmp(e, "8") != 0;
-        if (const char *e = lab_env("SDFHIP_MESH_FAIL_ALLOC")) fail_after = atoi(e);
-    }
-    bool refuse()                                   // is this allocation the one to fail?
-    {
-        if (fail_after == 0) { fail_after = -1; return true; }
-        if (fail_after > 0) fail_after--;
-        return false;
     }
 };
 
@@ -65,12 +58,7 @@ int check_options(const char *what, const sdfhip_mesh_options *opt, int32_t *lev
 {
     *level = -1;
     if (!opt) return SDFHIP_OK;
-    // the size rules of sdfhip_upload_options: version 1's 8 bytes or more; fields this library does not know must say "default" (-1)
-    if (opt->size < sizeof(sdfhip_mesh_options) || opt->size % 4u || opt->size > 4096u)
-        return fail(SDFHIP_ERR_ARG, "%s: options of %u bytes (sdfhip_mesh_options_default sets the size)", what, opt->size);
-    const int32_t *words = reinterpret_cast<const int32_t *>(opt);
-    for (uint32_t k = sizeof(sdfhip_mesh_options) / 4; k < opt->size / 4; k++)
-        if (words[k] != -1) return fail(SDFHIP_ERR_ARG, "%s: options of %u bytes with a field this library does not know set", what, opt->size);
+    if (const int rc = check_options_size(what, opt, sizeof(sdfhip_mesh_options), "sdfhip_mesh_options_default sets the size")) return rc;
     if (opt->level < -1 || opt->level > MESH_MAX_DEPTH)
         return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, opt->level, MESH_MAX_DEPTH);
     *level = opt->level;
@@ -98,7 +86,7 @@ int count_pass(sdfhip_scene *s, const char *what, Temp &t, Knobs &knobs, int32_t
     if (t.pending) { HIP_TRY(hipEventSynchronize(t.busy)); t.pending = false; }
     const uint32_t nchunk = chunks_of(s->n);
     const size_t need = HEAD_BYTES + (size_t)nchunk * sizeof(uint32_t);
-    if (knobs.refuse() || grow_buffer(t.buf, t.cap, need) != hipSuccess) {
+    if (knobs.alloc.next() || grow_buffer(t.buf, t.cap, need) != hipSuccess) {
         (void)hipGetLastError();
         return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %zu bytes of chunk totals", what, need);
     }
@@ -193,11 +181,11 @@ try {
         if (const int r = count_pass(scene, what, t, knobs, level, stats != nullptr, st, &h, &count_ms)) return r;
         if (!h.n_triangles) return SDFHIP_OK;
         const size_t bytes = (size_t)h.n_triangles * 18 * sizeof(float);
-        if (knobs.refuse() || grow_buffer(d_verts, d_cap, bytes) != hipSuccess) {
+        if (knobs.alloc.next() || grow_buffer(d_verts, d_cap, bytes) != hipSuccess) {
             (void)hipGetLastError();
             return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %llu triangles (%zu bytes)", what, h.n_triangles, bytes);
         }
-        verts = knobs.refuse() ? nullptr : static_cast<float *>(malloc(bytes));
+        verts = knobs.alloc.next() ? nullptr : static_cast<float *>(malloc(bytes));
         if (!verts) return fail(SDFHIP_ERR_NOMEM, "%s: out of host memory for %llu triangles (%zu bytes)", what, h.n_triangles, bytes);
         HIP_TRY(hipEventRecord(t.ev0, st));
         if (const int r = emit_pass(scene, t, knobs, level, d_verts, st)) return r;

@@ -20,6 +20,7 @@
 // keeps the temporary memory at four bytes per 1024 nodes.
 #pragma once
 #include "raymarch_device.h"
+#include "scan_device.h"     // block_exclusive_scan
 
 namespace sdfhip {
 
@@ -181,17 +182,10 @@ __global__ __launch_bounds__(1024) void k_mesh_scan(uint32_t *__restrict__ chunk
     const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
     unsigned long long sum = 0;
     for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {          // inclusive scan of the threads' sums (Hillis-Steele), as k_edit_scan_chunks
-        const unsigned long long v = t >= o ? part[t - o] : 0ull;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - sum;
+    unsigned long long total;
+    unsigned long long run = block_exclusive_scan<unsigned long long, 1024>(sum, part, total);
     for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = (uint32_t)run; run += v; }
-    if (t == 1023) head->n_triangles = part[1023];
+    if (t == 1023) head->n_triangles = total;
 }
 
 // A triangle is 72 bytes, so triangle k starts 8 bytes past a 16-byte boundary when k is odd: 16-byte stores with one 8-byte store in

@@ -17,7 +17,7 @@
 //   k_prune_expand      the internal nodes of level d -> those of level d + 1, from the root down: one list, the levels one
 //                       behind the other (one host synchronisation per level: its count sizes the next launch)
 //   k_prune_decide      per level from the deepest up: eight lanes per block, the verdict a ballot, a removed block's bits set
-//   k_prune_scan_*      the survivors' ranks: the edit's bitmap prefix, over the complement of the removed bits
+//   k_rank_scan_*       the survivors' ranks: the shared bitmap prefix (scan_device.h), over the complement of the removed bits
 //   k_prune_compact     the survivors to the result's arrays, links remapped
 // Then the arrays go to scene_from_arrays (grids, fused records) as the edit's do.
 #include "prune_kernels.h"
@@ -36,42 +36,17 @@ static_assert(sizeof(sdfhip_prune_options) == 12 && sizeof(sdfhip_prune_stats) =
 
 namespace {
 
-constexpr int PRUNE_MAX_DEPTH = 12;         // the deepest tree the grids and the cursor-stack kernels take (the edit's limit)
-constexpr int PRUNE_LEVELS = 16;            // counters (levels 0 .. PRUNE_MAX_DEPTH)
-
-struct NoMem {};
-
-// The prune's device memory, freed at the end (the arrays the scene is made from included: it keeps its own copy)
-struct Buffers {
-    std::vector<void *> owned;
-    int fail_after = -1;                    // laboratory library: SDFHIP_PRUNE_FAIL_ALLOC=k fails the k-th allocation (0 = the first)
-    ~Buffers() { for (void *p : owned) (void)hipFree(p); }
-    template <class T> T *get(size_t count)
-    {
-        void *p = nullptr;
-        if (fail_after == 0) throw NoMem{};
-        if (fail_after > 0) fail_after--;
-        const hipError_t e = device_alloc_bytes(&p, count ? count * sizeof(T) : 1);
-        if (e != hipSuccess) { (void)hipGetLastError(); throw NoMem{}; }
-        owned.push_back(p);
-        return static_cast<T *>(p);
-    }
-};
+constexpr int PRUNE_LEVELS = 16;            // counters (levels 0 .. TREE_MAX_DEPTH)
 
 int check_options(const sdfhip_prune_options *opt, int *tolerance, int *max_depth)
 {
     *tolerance = 0; *max_depth = -1;
     if (!opt) return SDFHIP_OK;
-    // the size rules of sdfhip_mesh_options: this version's bytes or more; fields this library does not know must say "default" (-1)
-    if (opt->size < sizeof(sdfhip_prune_options) || opt->size % 4u || opt->size > 4096u)
-        return fail(SDFHIP_ERR_ARG, "scene_prune: options of %u bytes (size = sizeof(sdfhip_prune_options))", opt->size);
-    const int32_t *words = reinterpret_cast<const int32_t *>(opt);
-    for (uint32_t k = sizeof(sdfhip_prune_options) / 4; k < opt->size / 4; k++)
-        if (words[k] != -1) return fail(SDFHIP_ERR_ARG, "scene_prune: options of %u bytes with a field this library does not know set", opt->size);
+    if (const int rc = check_options_size("scene_prune", opt, sizeof(sdfhip_prune_options), "size = sizeof(sdfhip_prune_options)")) return rc;
     if (opt->tolerance < -1 || opt->tolerance > 255)
         return fail(SDFHIP_ERR_ARG, "scene_prune: tolerance %d is neither -1 nor 0..255", opt->tolerance);
-    if (opt->max_depth < -1 || opt->max_depth > PRUNE_MAX_DEPTH)
-        return fail(SDFHIP_ERR_ARG, "scene_prune: max_depth %d is neither -1 nor 0..%d", opt->max_depth, PRUNE_MAX_DEPTH);
+    if (opt->max_depth < -1 || opt->max_depth > TREE_MAX_DEPTH)
+        return fail(SDFHIP_ERR_ARG, "scene_prune: max_depth %d is neither -1 nor 0..%d", opt->max_depth, TREE_MAX_DEPTH);
     *tolerance = opt->tolerance < 0 ? 0 : opt->tolerance;
     *max_depth = opt->max_depth;
     return SDFHIP_OK;
@@ -88,25 +63,16 @@ try {
     int tol = 0, maxd = -1;
     if (const int rc = check_options(opt, &tol, &maxd)) return rc;
     if (!scene) return fail(SDFHIP_ERR_ARG, "scene_prune: null argument");
-    if (!scene->stack_ok || scene->depth > (uint32_t)PRUNE_MAX_DEPTH)
-        return fail(SDFHIP_ERR_BAD_TREE, "scene_prune: the input tree is not consistent (or deeper than %d levels): no prune", PRUNE_MAX_DEPTH);
+    if (!scene->stack_ok || scene->depth > (uint32_t)TREE_MAX_DEPTH)
+        return fail(SDFHIP_ERR_BAD_TREE, "scene_prune: the input tree is not consistent (or deeper than %d levels): no prune", TREE_MAX_DEPTH);
 
     DeviceGuard g(scene->device);
     if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_prune: hipSetDevice(%d) failed", scene->device);
-    Buffers bufs;
-    if (const char *e = lab_env("SDFHIP_PRUNE_FAIL_ALLOC")) bufs.fail_after = atoi(e);
-    hipStream_t st = nullptr;
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    struct Release {
-        hipStream_t &st; hipEvent_t *ev;
-        ~Release()
-        {
-            if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-            for (int k = 0; k < 4; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-        }
-    } release{ st, ev };
-    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (int k = 0; k < 4; k++) HIP_TRY(hipEventCreate(&ev[k]));
+    DeviceBuffers bufs("SDFHIP_PRUNE_FAIL_ALLOC");
+    CallStream<4> cs;                       // (after `bufs`: drained before the buffers are freed)
+    if (const int rc = cs.open("")) return rc;
+    const hipStream_t st = cs.st;
+    const hipEvent_t *ev = cs.ev;
 
     const uint32_t n = scene->n;
     const uint32_t cap = (n - 1) / 8;                       // a consistent tree's internal nodes: every other node lies in one's block
@@ -121,7 +87,6 @@ try {
         PruneCounters *cnt = bufs.get<PruneCounters>(PRUNE_LEVELS);
         HIP_TRY(hipMemsetAsync(removed, 0, ((size_t)words + 1) * sizeof(uint32_t), st));
         HIP_TRY(hipMemsetAsync(cnt, 0, PRUNE_LEVELS * sizeof(PruneCounters), st));
-        const auto grid_of = [](uint64_t threads) { return dim3((uint32_t)std::min<uint64_t>((threads + 255) / 256, 4096)); };
 
         // the blocks to their levels: level d's parents at list[off[d] .. off[d] + count[d])
         NodeRec root;
@@ -137,8 +102,8 @@ try {
         for (int d = 0; count[d]; d++) {
             levels = d + 1;
             off[d + 1] = off[d] + count[d];
-            if (d >= PRUNE_MAX_DEPTH) return fail(SDFHIP_ERR_BAD_TREE, "scene_prune: the walk went deeper than %d levels", PRUNE_MAX_DEPTH);
-            hipLaunchKernelGGL(k_prune_expand, grid_of(8ull * count[d]), dim3(256), 0, st, scene->nodes, n, list + off[d], count[d],
+            if (d >= TREE_MAX_DEPTH) return fail(SDFHIP_ERR_BAD_TREE, "scene_prune: the walk went deeper than %d levels", TREE_MAX_DEPTH);
+            hipLaunchKernelGGL(k_prune_expand, grid_stride_blocks(8ull * count[d]), dim3(256), 0, st, scene->nodes, n, list + off[d], count[d],
                                list + off[d + 1], cap - off[d + 1], cnt + d + 1);
             HIP_TRY(hipGetLastError());
             PruneCounters c;
@@ -151,12 +116,12 @@ try {
         // the verdicts, from the deepest level up
         for (int d = levels - 1; d >= 0; d--) {
             const int cut = maxd >= 0 && d + 1 > maxd ? 1 : 0;
-            hipLaunchKernelGGL(k_prune_decide, grid_of(8ull * count[d]), dim3(256), 0, st, scene->nodes, n, list + off[d], count[d],
+            hipLaunchKernelGGL(k_prune_decide, grid_stride_blocks(8ull * count[d]), dim3(256), 0, st, scene->nodes, n, list + off[d], count[d],
                                ldexpf(1.0f, -d), cut, tol, removed, cnt + d);
         }
         // the survivors' ranks
-        hipLaunchKernelGGL(k_prune_scan_words, dim3(nchunk), dim3(256), 0, st, removed, n, words, pre, chunk);
-        hipLaunchKernelGGL(k_prune_scan_chunks, dim3(1), dim3(1024), 0, st, chunk, nchunk);
+        hipLaunchKernelGGL(k_rank_scan_words<PruneKeepWords>, dim3(nchunk), dim3(256), 0, st, PruneKeepWords{ removed, n }, words, pre, chunk);
+        hipLaunchKernelGGL(k_rank_scan_chunks<true>, dim3(1), dim3(1024), 0, st, chunk, nchunk);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[1], st));
         PruneCounters c[PRUNE_LEVELS];
@@ -173,7 +138,7 @@ try {
         dS = bufs.get<int2>(n_out);
         dV = bufs.get<uint2>(n_out);
         HIP_TRY(hipEventRecord(ev[2], st));
-        hipLaunchKernelGGL(k_prune_compact, grid_of(n), dim3(256), 0, st, scene->nodes, n, removed, pre, chunk, n_out, dS, dV);
+        hipLaunchKernelGGL(k_prune_compact, grid_stride_blocks(n), dim3(256), 0, st, scene->nodes, n, removed, pre, chunk, n_out, dS, dV);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[3], st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -184,28 +149,14 @@ try {
     HIP_TRY(hipEventElapsedTime(&ms_a, ev[0], ev[1]));
     HIP_TRY(hipEventElapsedTime(&ms_b, ev[2], ev[3]));
 
-    const auto t1 = std::chrono::steady_clock::now();
-    sdfhip_scene *res = nullptr;
-    const int rc = scene_from_arrays(scene->device, reinterpret_cast<const int32_t *>(dS), reinterpret_cast<const uint8_t *>(dV), n_out, true,
-                                     nullptr, &res, (int)depth_out);
-    if (rc != SDFHIP_OK) return rc;
-    const float scene_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    if (host_out) {
-        bool no_host_memory = false;
-        const hipError_t e = tree_to_host(dS, dV, n_out, malloc, host_out, &no_host_memory);
-        if (e != hipSuccess) {
-            (void)sdfhip_scene_free(res);
-            return no_host_memory ? fail(SDFHIP_ERR_NOMEM, "scene_prune: out of host memory for host_out")
-                                  : fail(SDFHIP_ERR_DEVICE, "scene_prune: copying the tree to the host failed: %s", hipGetErrorString(e));
-        }
-    }
+    float scene_ms = 0.0f;
+    if (const int rc = finish_tree("scene_prune", scene->device, dS, dV, n_out, (int)depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_in = n; stats->nodes_out = n_out;
         stats->blocks_removed = blocks_removed; stats->depth_out = depth_out;
         stats->kernel_ms = ms_a + ms_b; stats->scene_ms = scene_ms;
         stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    *out = res;
     return SDFHIP_OK;
 }
 SDFHIP_ABI_CATCH(sdfhip_scene_prune)

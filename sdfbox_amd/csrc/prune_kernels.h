@@ -1,5 +1,5 @@
 // The prune's kernels (gfx950): the internal nodes brought to their levels, the blocks of eight judged level by level from the deepest
-// up, a prefix scan over the bitmap of survivors and one compaction.  Non-template kernels: included by prune.hip ONLY.
+// up, the survivors' ranks by the shared bitmap scan (scan_device.h) and one compaction.  Non-template kernels: included by prune.hip ONLY.
 //
 // The arithmetic is the contract of include/sdfhip.h (sdfhip_scene_prune) and DESIGN.md section 8 (N9): fp32, each operation rounded
 // on its own, in the order written (-ffp-contract=off); tests/prune_restatement.py restates it with numpy, level by level.  The
@@ -9,6 +9,7 @@
 #include "raymarch_device.h"
 #include "sdf_bytes.h"
 #include "sdf_interp.h"
+#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap
 
 namespace sdfhip {
 
@@ -101,56 +102,18 @@ __device__ __forceinline__ uint32_t prune_keep_word(const uint32_t *__restrict__
     return ~removed[w] & (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
 }
 
-// The prefix counts of the survivors' bitmap, words 0 .. m - 1: per word, the survivors of the words before it in its chunk of 1024
-// words (pre[]), and per chunk its total (chunk[]) -- the edit's scan (k_edit_scan_words) over the complement of removed[]
-__global__ __launch_bounds__(256) void k_prune_scan_words(const uint32_t *__restrict__ removed, uint32_t n, uint32_t m,
-                                                          uint32_t *__restrict__ pre, uint32_t *__restrict__ chunk)
-{
-    __shared__ uint32_t part[256];
-    const uint32_t t = threadIdx.x, first = blockIdx.x * 1024u + 4u * t;
-    uint32_t c[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { c[k] = first + k < m ? (uint32_t)__popc(prune_keep_word(removed, first + k, n)) : 0u; sum += c[k]; }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {          // inclusive scan of the threads' sums (Hillis-Steele)
-        const uint32_t v = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (first + k < m) pre[first + k] = run; run += c[k]; }
-    if (t == 255) chunk[blockIdx.x] = part[255];
-}
-
-// ... the chunks' totals -> exclusive prefix, in one workgroup (at most 65 536 chunks: 2^31 nodes); chunk[nchunk] = the survivors
-__global__ __launch_bounds__(1024) void k_prune_scan_chunks(uint32_t *__restrict__ chunk, uint32_t nchunk)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
-    uint32_t sum = 0;
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = run; run += v; }
-    if (t == 1023) chunk[nchunk] = part[1023];
-}
+// The survivors' bitmap, words 0 .. m - 1, to k_rank_scan_words (scan_device.h): the complement of removed[]
+struct PruneKeepWords {
+    const uint32_t *removed;
+    uint32_t n;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return prune_keep_word(removed, i, n); }
+};
 
 // a survivor's new index: the survivors with a lower old index
 __device__ __forceinline__ uint32_t prune_rank(const uint32_t *__restrict__ removed, const uint32_t *__restrict__ pre,
                                                const uint32_t *__restrict__ chunk, uint32_t i)
 {
-    const uint32_t w = i >> 5;
-    return chunk[w >> 10] + pre[w] + (uint32_t)__popc(~removed[w] & ((1u << (i & 31u)) - 1u));
+    return rank_in_bitmap(chunk, pre, i >> 5, ~removed[i >> 5], i & 31u);
 }
 
 // The survivors, in their order, to the arrays of the result: {parent, children} remapped -- a node whose block was removed becomes

@@ -22,6 +22,11 @@ inline const char *lab_env(const char *name) { return getenv(name); }
 inline const char *lab_env(const char *) { return nullptr; }
 #endif
 
+// The size rules of a versioned options record (sdfhip_mesh_options, sdfhip_prune_options, sdfhip_trimesh_options; its first field is
+// `uint32_t size`): this version's `known_bytes` or more, a multiple of 4, at most 4096, and every word this library does not know
+// says "default" (-1).  hint: how the caller sets the size, for the message.
+int check_options_size(const char *what, const void *opt, uint32_t known_bytes, const char *hint);
+
 // sdfhip_scene_upload[_ex], or the same from arrays that are already in `device`'s memory (sdfhip_sdfgen_scene); opt may be null
 // trusted_depth >= 0: the arrays are the GPU builder's own output -- consistent by construction, that deep -- and are not validated again
 int scene_from_arrays(int device, const int32_t *structs, const uint8_t *values, uint32_t n, bool resident, const sdfhip_upload_options *opt,

@@ -24,33 +24,23 @@ static_assert(sizeof(sdfhip_trimesh_stats) == 40 && sizeof(TriBlock) == 32, "the
 
 namespace {
 
-constexpr int TRI_MAX_DEPTH = 12;
 constexpr uint32_t TRI_WIDE_BLOCKS = 512;     // fewer blocks than this: 16 waves per block instead of 4 (the first levels' lists are long)
-
-struct NoMem {};
 
 struct Level { int2 *S; uint2 *V; uint32_t n; };
 
-// laboratory library: SDFHIP_TRI_PRUNE=0 -- every block keeps every record (the A/B, and the test that pruning changes no byte);
-// SDFHIP_TRI_FAIL_ALLOC=k fails the build's k-th allocation (0 = the first)
+// laboratory library: SDFHIP_TRI_PRUNE=0 -- every block keeps every record (the A/B, and the test that pruning changes no byte)
 struct Knobs {
     bool prune = true;
-    int fail_after = -1;
-    Knobs()
-    {
-        if (const char *e = lab_env("SDFHIP_TRI_PRUNE")) prune = atoi(e) != 0;
-        if (const char *e = lab_env("SDFHIP_TRI_FAIL_ALLOC")) fail_after = atoi(e);
-    }
+    Knobs() { if (const char *e = lab_env("SDFHIP_TRI_PRUNE")) prune = atoi(e) != 0; }
 };
 
+// The build's arenas; laboratory library: SDFHIP_TRI_FAIL_ALLOC=k fails the build's k-th allocation (0 = the first)
 struct Memory {
     Arena keep{ (size_t)32 << 20 }, scratch[2] = { Arena((size_t)32 << 20), Arena((size_t)32 << 20) };
-    int fail_after;
-    explicit Memory(int fail_after) : fail_after(fail_after) {}
+    AllocFault fault{ "SDFHIP_TRI_FAIL_ALLOC" };
     template <class T> T *get(Arena &a, size_t n)
     {
-        if (fail_after == 0) throw NoMem{};
-        if (fail_after > 0) fail_after--;
+        if (fault.next()) throw NoMem{};
         T *p = a.alloc<T>(n);
         if (!p) throw NoMem{};
         return p;
@@ -78,7 +68,7 @@ try {
     if (host_out) { host_out->length = 0; host_out->structs = nullptr; host_out->values = nullptr; }
     if (!mesh || !mesh->records || mesh->n_records == 0) return fail(SDFHIP_ERR_ARG, "trimesh_build: null mesh or no records");
     if (!scene && !host_out) return fail(SDFHIP_ERR_ARG, "trimesh_build: neither a scene nor host arrays asked for");
-    if (depth < 0 || depth > TRI_MAX_DEPTH) return fail(SDFHIP_ERR_ARG, "trimesh_build: depth %d outside 0..%d", depth, TRI_MAX_DEPTH);
+    if (depth < 0 || depth > TREE_MAX_DEPTH) return fail(SDFHIP_ERR_ARG, "trimesh_build: depth %d outside 0..%d", depth, TREE_MAX_DEPTH);
     const uint32_t nrec = mesh->n_records;
     // the pruning's absolute slack: 2^-14 of the largest coordinate in play, the cube's own 1 at least
     float bound = 1.0f;
@@ -92,16 +82,11 @@ try {
     DeviceGuard g(device);
     if (!g.ok) return fail(SDFHIP_ERR_DEVICE, "trimesh_build: hipSetDevice(%d) failed", device);
     const Knobs knobs;
-    Memory mem(knobs.fail_after);
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Release {
-        hipStream_t &st; hipEvent_t &a, &b;
-        ~Release() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } release{ st, ev0, ev1 };          // (declared after `mem`: the stream is drained before the arenas give their chunks back)
-    TRI_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    TRI_TRY(hipEventCreate(&ev0));
-    TRI_TRY(hipEventCreate(&ev1));
+    Memory mem;
+    CallStream<2> cs;                       // (after `mem`: drained before the arenas give their chunks back)
+    if (const int rc = cs.open("trimesh_build: ")) return rc;
+    const hipStream_t st = cs.st;
+    const hipEvent_t ev0 = cs.ev[0], ev1 = cs.ev[1];
 
     std::vector<Level> levels;
     uint64_t total_nodes = 0, cand_entries = 0;
@@ -183,30 +168,14 @@ try {
     float build_ms = 0.0f;
     TRI_TRY(hipEventElapsedTime(&build_ms, ev0, ev1));
 
-    const auto t1 = std::chrono::steady_clock::now();
-    sdfhip_scene *res = nullptr;
-    if (scene) {
-        const int rc = scene_from_arrays(device, reinterpret_cast<const int32_t *>(dS), reinterpret_cast<const uint8_t *>(dV), (uint32_t)total_nodes,
-                                         true, nullptr, &res, (int)levels.size() - 1);
-        if (rc != SDFHIP_OK) return rc;
-    }
-    const float scene_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    if (host_out) {
-        bool no_host_memory = false;
-        const hipError_t e = tree_to_host(dS, dV, total_nodes, malloc, host_out, &no_host_memory);
-        if (e != hipSuccess) {
-            if (res) (void)sdfhip_scene_free(res);
-            return no_host_memory ? fail(SDFHIP_ERR_NOMEM, "trimesh_build: out of host memory for host_out")
-                                  : fail(SDFHIP_ERR_DEVICE, "trimesh_build: copying the tree to the host failed: %s", hipGetErrorString(e));
-        }
-    }
+    float scene_ms = 0.0f;
+    if (const int rc = finish_tree("trimesh_build", device, dS, dV, (uint32_t)total_nodes, (int)levels.size() - 1, scene, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes = (uint32_t)total_nodes; stats->levels = (uint32_t)levels.size(); stats->records = nrec; stats->pad_ = 0;
         stats->candidate_entries = cand_entries;
         stats->build_ms = build_ms; stats->scene_ms = scene_ms; stats->pad1_ = 0;
         stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    if (scene) *scene = res;
     return SDFHIP_OK;
 }
 SDFHIP_ABI_CATCH(sdfhip_trimesh_build)

@@ -14,6 +14,7 @@
 // The arithmetic of tri_dist2 and of the value in k_tri_eval is the pinned rule of include/sdfhip.h, operation for operation (-ffp-contract=off).
 #pragma once
 #include "sdf_bytes.h"
+#include "scan_device.h"     // block_exclusive_scan
 
 namespace sdfhip {
 
@@ -216,24 +217,7 @@ __global__ __launch_bounds__(TRI_COUNT_THREADS) void k_tri_count(const float *__
 }
 
 // ---- exclusive scan of n uint32 into uint64, with the total --------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long tri_block_scan(unsigned long long v, unsigned long long *sh, unsigned long long &total)
-{
-    // inclusive Hillis-Steele over the workgroup's TRI_SCAN_THREADS values; returns the exclusive prefix
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < TRI_SCAN_THREADS; d <<= 1) {
-        const unsigned long long add = t >= d ? sh[t - d] : 0ull;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    total = sh[TRI_SCAN_THREADS - 1];
-    const unsigned long long excl = sh[t] - v;
-    __syncthreads();
-    return excl;
-}
-
+// (block_exclusive_scan, scan_device.h, over the workgroup's TRI_SCAN_THREADS partial sums)
 __global__ __launch_bounds__(TRI_SCAN_THREADS) void k_tri_scan_sums(const uint32_t *__restrict__ in, uint32_t n, unsigned long long *sums)
 {
     __shared__ unsigned long long sh[TRI_SCAN_THREADS];
@@ -241,7 +225,7 @@ __global__ __launch_bounds__(TRI_SCAN_THREADS) void k_tri_scan_sums(const uint32
     unsigned long long v = 0;
     for (uint32_t k = 0; k < 4; k++) if (i0 + k < n) v += in[i0 + k];
     unsigned long long total;
-    (void)tri_block_scan(v, sh, total);
+    (void)block_exclusive_scan<unsigned long long, TRI_SCAN_THREADS>(v, sh, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -254,7 +238,7 @@ __global__ __launch_bounds__(TRI_SCAN_THREADS) void k_tri_scan_chunks(unsigned l
         const uint32_t i = base + threadIdx.x;
         const unsigned long long v = i < nchunk ? sums[i] : 0ull;
         unsigned long long total;
-        const unsigned long long excl = tri_block_scan(v, sh, total);
+        const unsigned long long excl = block_exclusive_scan<unsigned long long, TRI_SCAN_THREADS>(v, sh, total);
         if (i < nchunk) sums[i] = carry + excl;
         carry += total;
     }
@@ -270,7 +254,7 @@ __global__ __launch_bounds__(TRI_SCAN_THREADS) void k_tri_scan_apply(const uint3
     unsigned long long v = 0;
     for (uint32_t k = 0; k < 4; k++) { x[k] = i0 + k < n ? in[i0 + k] : 0u; v += x[k]; }
     unsigned long long total;
-    unsigned long long run = sums[blockIdx.x] + tri_block_scan(v, sh, total);
+    unsigned long long run = sums[blockIdx.x] + block_exclusive_scan<unsigned long long, TRI_SCAN_THREADS>(v, sh, total);
     for (uint32_t k = 0; k < 4; k++) { if (i0 + k < n) out[i0 + k] = run; run += x[k]; }
 }
 

@@ -46,12 +46,7 @@ int check_options(const sdfhip_trimesh_options *opt, int32_t *fit, float *fill)
 {
     *fit = 0; *fill = 0.8f;
     if (!opt) return SDFHIP_OK;
-    // the size rules of sdfhip_mesh_options: this version's bytes or more; fields this library does not know must say "default" (-1)
-    if (opt->size < sizeof(sdfhip_trimesh_options) || opt->size % 4u || opt->size > 4096u)
-        return fail(SDFHIP_ERR_ARG, "trimesh_prepare: options of %u bytes (sdfhip_trimesh_options_default sets the size)", opt->size);
-    const int32_t *words = reinterpret_cast<const int32_t *>(opt);
-    for (uint32_t k = sizeof(sdfhip_trimesh_options) / 4; k < opt->size / 4; k++)
-        if (words[k] != -1) return fail(SDFHIP_ERR_ARG, "trimesh_prepare: options of %u bytes with a field this library does not know set", opt->size);
+    if (const int rc = check_options_size("trimesh_prepare", opt, sizeof(sdfhip_trimesh_options), "sdfhip_trimesh_options_default sets the size")) return rc;
     if (opt->fit < -1 || opt->fit > 1) return fail(SDFHIP_ERR_ARG, "trimesh_prepare: fit %d is none of -1, 0, 1", opt->fit);
     if (opt->fit == 1) *fit = 1;
     if (opt->fill != -1.0f) {

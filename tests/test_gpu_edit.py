@@ -71,6 +71,17 @@ def assert_same_tree(od, S, V, what):
                                                 [(od.Values[i].tolist(), V[i].tolist()) for i in bad_v[:3]])
 
 
+def split_windows(S, nodes_in):
+    """{depth: (lowest, highest)} over the parents of an edit's new blocks (the nodes whose children link is >= nodes_in): per
+    level, the span of the split bitmap that the edit ranks"""
+    parents = np.nonzero(S[:, 1] >= nodes_in)[0]
+    depth, up = np.zeros(len(parents), dtype=np.int64), S[parents, 0].astype(np.int64)
+    while (up >= 0).any():
+        depth[up >= 0] += 1
+        up = np.where(up >= 0, S[np.maximum(up, 0), 0], -1)
+    return {int(d): (int(parents[depth == d].min()), int(parents[depth == d].max())) for d in np.unique(depth)}
+
+
 @pytest.mark.parametrize("name", ["sphere_d4", "torus_d6", "gyroid_d8", "builder_d10"])
 def test_edited_bytes_are_the_restatements(sb, name):
     od = tree(name)
@@ -80,6 +91,11 @@ def test_edited_bytes_are_the_restatements(sb, name):
         for where, op, brush, params in brushes(od, small):
             for md in ((-1, d0 + 1) if d0 < 12 else (-1,)):
                 S, V = er.edit(od.Structs, od.Values, [(op, brush, params)], md, region=not small)
+                if name == "gyroid_d8" and where == "surface" and md == d0 + 1:
+                    # the window form of the shared word scan (k_rank_scan_words): the deepest level's splits are ranked over a
+                    # window of the bitmap that does not start at word 0 and spans more than one chunk of 1024 words
+                    lowest, highest = split_windows(S, od.Length)[d0]
+                    assert lowest >> 5 > 0 and (highest >> 5) - (lowest >> 5) >= 1024, (op, brush, lowest, highest)
                 res, got, st = gpu_edit(sb, scene, [(op, brush, params)], None if md < 0 else md)
                 with res:
                     what = f"{name} {where} op={op} brush={brush} max_depth={md}"
