@@ -202,6 +202,20 @@ public:
         sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Combination (sdfhip_scene_combine): the loaded model becomes its union (SDFHIP_COMBINE_UNION), intersection (_INTERSECT) or
+    // difference (_SUBTRACT: this model without the other) with the model `other` has loaded on the same device (it may be this
+    // Program); both live in the same unit cube, nothing is placed, blended or pruned (chain Prune(0)).  The result replaces the
+    // loaded model as Prune's does; `other` keeps its own.  max_depth: -1 = no cut, else 0..12.  host_out (may be null): the result's
+    // host arrays
+    void Combine(const Program &other, int op, int max_depth = -1, sdfhip_combine_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        if (!scene || !other.scene) throw Error(SDFHIP_ERR_ARG, "Combine: no model loaded");
+        const sdfhip_combine_options opt = { (uint32_t)sizeof(sdfhip_combine_options), max_depth };
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_combine(scene, other.scene, op, &opt, &fresh, host_out, stats));
+        sdfhip_scene_free(scene);
+        scene = fresh;
+    }
     // Point and ray queries (sdfhip_scene_sample / _raycast / _pick; nothing in the reference corresponds): what the loaded model
     // answers without drawing a frame, with the shader's own arithmetic.  Sample: distance, cell and gradient at points (xyz: 3 floats
     // per point); Raycast: the primary march of Compute.hlsl:194-203 for arbitrary rays; Pick: that march for pixels {x, y} of the

@@ -533,6 +533,55 @@ typedef struct sdfhip_prune_stats {
 SDFHIP_API int sdfhip_scene_prune(sdfhip_scene *scene, const sdfhip_prune_options *opt, sdfhip_scene **out, sdfhip_octdata *host_out,
                                   sdfhip_prune_stats *stats);
 
+/* ---- combination: the union, intersection or difference of two resident scenes -----------------------
+ * Replaces: nothing in the reference's code -- a tree there is immutable once built and its only consumer draws one tree; two
+ * models could meet only as triangles, before a rebuild.
+ * sdfhip_scene_combine combines the trees of `a` and `b`, which live in the same unit cube on the same device, and returns the result
+ * as a NEW handle `*out` on that device: both inputs are untouched (frames in flight on them included), any of the three handles may
+ * be freed first, and a == b is allowed.  Calls on the operands from other threads (renders, queries) do not wait for the
+ * combination: it holds the handles' locks only while it reads what they describe.  Every octree cell of one operand has the same address in the other, so nothing is
+ * resampled: the trees leave HBM only for host_out.  There is no placement of an operand (that stays with the builders), no
+ * blending, and nothing is pruned.  The rule, pinned (fp32, each operation rounded on its own in the order written, as the edit's and
+ * the prune's; S = 2^-d the edge of a cell of depth d):
+ *   cells            a cell of depth d is a node of the result iff it is a node of A or of B (the root always is).  A result node has
+ *                    a block of eight children iff A's node there has children or B's has, and d < max_depth when a cut is given
+ *   operand bytes    at a result cell, operand X's own eight bytes if X has this node.  Otherwise they are inherited: starting from
+ *                    X's leaf that contains the cell, sdfhip_scene_prune's inherited byte q(i, k) is applied once per level down to
+ *                    the cell, re-quantising at every level -- sdfhip_scene_edit's rule for new children, iterated
+ *   negation         SUBTRACT only, applied to B's bytes at the result cell, after the inheritance:
+ *                    neg(b) = floorf(saturate(-f / 2 / S + 0.25f) * 255), f = ((b / 255.0f) - 0.25f) * S * 2.0f; byte 63 becomes 64
+ *                    and 64 becomes 63, so the sign flips exactly at the surface
+ *   result byte      per corner: UNION min(a, b); INTERSECT max(a, b); SUBTRACT max(a, neg(b))
+ *   node order       breadth first, as sdfhip_trimesh_build's: node 0 is the root (parent -1); a level's child blocks follow in
+ *                    ascending result index of the parent; child i is at block + i; a leaf's children field is -1.  Bytes and links
+ *                    depend on the operands' arrays, the op and the option alone, never on which wave finished first
+ *   nothing is pruned  nodes_out <= nodes_a + nodes_b - 1.  Where one operand wins outright the other's structure stays in the
+ *                    result with interpolated bytes; sdfhip_scene_prune at tolerance 0 on the result removes exactly those blocks
+ * opt: NULL = defaults.  max_depth: -1 = no cut, else 0..12.  The struct grows like sdfhip_prune_options: the caller sets size =
+ * sizeof(sdfhip_combine_options); a larger, newer struct is accepted when the fields this library does not know are all -1.
+ * host_out (may be NULL): the result's host arrays (release with sdfhip_octdata_free).  stats (may be NULL).
+ * SDFHIP_ERR_ARG: a null scene or output, an unknown op, max_depth outside -1..12, an options struct the size rules refuse, operands
+ * on different devices, a result of more than 2^31 - 1 nodes; SDFHIP_ERR_BAD_TREE: either operand is not consistent
+ * (stack_kernel_ok == 0 in sdfhip_scene_info) or deeper than 12 levels, as sdfhip_scene_prune refuses it; SDFHIP_ERR_NOMEM: out of
+ * device memory (both inputs stay valid, nothing leaks).
+ * Work is proportional to the result: every record of both operands is read once or twice, every result node written; the call's
+ * device memory is sized for nodes_a + nodes_b - 1 nodes (or the full tree of max_depth, if smaller); the new handle builds its
+ * lookup grids anew. */
+enum { SDFHIP_COMBINE_UNION = 0, SDFHIP_COMBINE_INTERSECT = 1, SDFHIP_COMBINE_SUBTRACT = 2 };   /* A or B, A and B, A without B */
+typedef struct sdfhip_combine_options {
+    uint32_t size;          /* sizeof(sdfhip_combine_options) of the caller's header */
+    int32_t max_depth;      /* -1 = no cut; 0..12: no result node is deeper */
+} sdfhip_combine_options;
+typedef struct sdfhip_combine_stats {
+    uint32_t nodes_a, nodes_b, nodes_out, depth_out;
+    uint32_t nodes_shared;   /* result cells that are nodes of both operands */
+    float kernel_ms;         /* HIP events around the combination's kernels (the per-level host synchronisations included) */
+    float scene_ms;          /* building the new handle (fused records, lookup grids), host clock */
+    float total_ms;          /* host clock, the whole call */
+} sdfhip_combine_stats;      /* 32 bytes */
+SDFHIP_API int sdfhip_scene_combine(sdfhip_scene *a, sdfhip_scene *b, int32_t op, const sdfhip_combine_options *opt,
+                                    sdfhip_scene **out, sdfhip_octdata *host_out, sdfhip_combine_stats *stats);
+
 /* ---- point and ray queries: what a resident scene answers without drawing a frame -------------------
  * Replaces: nothing in the reference's code -- its only consumer of the tree is Compute.hlsl; a host that wants the distance at a
  * point (collision, placement, snapping) or the surface point under the cursor (where to put a brush) has no call to make there.

@@ -44,13 +44,14 @@ TUNE_BYTE_CELLS = 0x200000    # on a scene uploaded under SDFHIP_SAMPLE_RECORDS=
 SHAPE_SPHERE, SHAPE_TORUS, SHAPE_GYROID = 0, 1, 2
 EDIT_CARVE, EDIT_ADD = 0, 1          # sdfhip_scene_edit: subtract / union
 BRUSH_SPHERE, BRUSH_BOX = 0, 1
+COMBINE_UNION, COMBINE_INTERSECT, COMBINE_SUBTRACT = 0, 1, 2      # sdfhip_scene_combine: A or B, A and B, A without B
 QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdfhip_probe.status / sdfhip_hit.status
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -172,6 +173,22 @@ else:
 
 
     assert (ctypes.sizeof(PruneOptions), ctypes.sizeof(PruneStats)) == (12, 28)
+
+
+    class CombineOptions(ctypes.Structure):
+        """sdfhip_combine_options: max_depth None = no cut, else 0..12."""
+        _fields_ = [("size", ctypes.c_uint32), ("max_depth", ctypes.c_int32)]
+
+        def __init__(self, max_depth=None):
+            super().__init__(ctypes.sizeof(type(self)), -1 if max_depth is None else int(max_depth))
+
+
+    class CombineStats(ctypes.Structure):
+        _fields_ = [("nodes_a", ctypes.c_uint32), ("nodes_b", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32),
+                    ("nodes_shared", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(CombineOptions), ctypes.sizeof(CombineStats)) == (8, 32)
 
 
     class Probe(ctypes.Structure):
@@ -299,6 +316,7 @@ _SIG = {
     "sdfhip_scene_edit": (_c.c_int, [_vp, _c.POINTER(Edit), _c.c_uint32, _c.c_int32, _c.POINTER(_vp), _c.POINTER(COctData),
                                      _c.POINTER(EditStats)]),
     "sdfhip_scene_prune": (_c.c_int, [_vp, _c.POINTER(PruneOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PruneStats)]),
+    "sdfhip_scene_combine": (_c.c_int, [_vp, _vp, _c.c_int32, _c.POINTER(CombineOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(CombineStats)]),
     "sdfhip_scene_sample": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
     "sdfhip_scene_sample_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),

@@ -161,6 +161,29 @@ class Scene:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
 
+    def Combine(self, other, op, max_depth=None, want_octdata=False, want_stats=False):
+        """Combination (sdfhip_scene_combine): the union (COMBINE_UNION), intersection (COMBINE_INTERSECT) or difference
+        (COMBINE_SUBTRACT: this scene without `other`) of this scene and `other`, a Scene on the same device (it may be this one); both
+        live in the same unit cube, nothing is placed, blended or pruned (chain Prune(0)).  max_depth: None = no cut, else 0..12.
+        The result is a NEW Scene in breadth-first order, both inputs are left as they were.  want_octdata: also the result's host
+        arrays; want_stats: a CombineStats."""
+        from .octdata import OctData
+        opt = _lib.CombineOptions(max_depth)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = self.device
+        raw = _lib.COctData()
+        st = _lib.CombineStats()
+        check(lib.sdfhip_scene_combine(self._h, other._h, int(op), ctypes.byref(opt), ctypes.byref(res._h),
+                                       ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
     # -- point and ray queries (sdfhip_scene_sample / _raycast / _pick): answers without a frame ---------------------------------
     def Sample(self, points):
         """Distance, cell and gradient at points (n, 3) float32, with the shader's own arithmetic: a structured array of n records
