@@ -204,7 +204,7 @@ public:
     }
     // Combination (sdfhip_scene_combine): the loaded model becomes its union (SDFHIP_COMBINE_UNION), intersection (_INTERSECT) or
     // difference (_SUBTRACT: this model without the other) with the model `other` has loaded on the same device (it may be this
-    // Program); both live in the same unit cube, nothing is placed, blended or pruned (chain Prune(0)).  The result replaces the
+    // Program); both live in the same unit cube (Place one first to move it), nothing is blended or pruned (chain Prune(0)).  The result replaces the
     // loaded model as Prune's does; `other` keeps its own.  max_depth: -1 = no cut, else 0..12.  host_out (may be null): the result's
     // host arrays
     void Combine(const Program &other, int op, int max_depth = -1, sdfhip_combine_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
@@ -213,6 +213,27 @@ public:
         const sdfhip_combine_options opt = { (uint32_t)sizeof(sdfhip_combine_options), max_depth };
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_combine(scene, other.scene, op, &opt, &fresh, host_out, stats));
+        sdfhip_scene_free(scene);
+        scene = fresh;
+    }
+    // Placement (sdfhip_scene_place): the loaded model is rotated, scaled and moved -- a point x of it lands at scale * R x + t, R
+    // row-major and orthogonal (a mirror is allowed), scale > 0 -- by resampling it into a new tree of at most `depth` levels (-1 = the
+    // model's own depth, else 0..12), which replaces the loaded model as Prune's result does.  Nothing is pruned (chain Prune), and the
+    // identity is a resampling, not a clone.  Place two Programs, then Combine them.  host_out (may be null): the result's host arrays
+    void Place(const float (&rotation)[3][3], float scale, const float (&translation)[3], int depth = -1, sdfhip_place_stats *stats = nullptr,
+               sdfhip_octdata *host_out = nullptr)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Place: no model loaded");
+        sdfhip_placement pl = {};
+        pl.size = (uint32_t)sizeof(sdfhip_placement);
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) pl.rotation[i][j] = rotation[i][j];
+            pl.translation[i] = translation[i];
+        }
+        pl.scale = scale;
+        pl.depth = depth;
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_place(scene, &pl, &fresh, host_out, stats));
         sdfhip_scene_free(scene);
         scene = fresh;
     }

@@ -540,7 +540,7 @@ SDFHIP_API int sdfhip_scene_prune(sdfhip_scene *scene, const sdfhip_prune_option
  * as a NEW handle `*out` on that device: both inputs are untouched (frames in flight on them included), any of the three handles may
  * be freed first, and a == b is allowed.  Calls on the operands from other threads (renders, queries) do not wait for the
  * combination: it holds the handles' locks only while it reads what they describe.  Every octree cell of one operand has the same address in the other, so nothing is
- * resampled: the trees leave HBM only for host_out.  There is no placement of an operand (that stays with the builders), no
+ * resampled: the trees leave HBM only for host_out.  An operand is placed beforehand (sdfhip_scene_place, below); there is no
  * blending, and nothing is pruned.  The rule, pinned (fp32, each operation rounded on its own in the order written, as the edit's and
  * the prune's; S = 2^-d the edge of a cell of depth d):
  *   cells            a cell of depth d is a node of the result iff it is a node of A or of B (the root always is).  A result node has
@@ -581,6 +581,64 @@ typedef struct sdfhip_combine_stats {
 } sdfhip_combine_stats;      /* 32 bytes */
 SDFHIP_API int sdfhip_scene_combine(sdfhip_scene *a, sdfhip_scene *b, int32_t op, const sdfhip_combine_options *opt,
                                     sdfhip_scene **out, sdfhip_octdata *host_out, sdfhip_combine_stats *stats);
+
+/* ---- placement: a resident scene rotated, scaled and moved by resampling ----------------------------
+ * Replaces: nothing in the reference's code -- a tree there sits where its builder put it; a model that was loaded, built from
+ * points or carved could be moved only as triangles, before a rebuild, losing everything below the mesh's resolution.
+ * sdfhip_scene_place resamples the tree of `scene` under the similarity p = s * R x + t (a source point x lands at p) into a new tree
+ * and returns it as a NEW handle `*out` on the same device: the input is untouched (frames in flight on it included) and either
+ * handle may be freed first.  Calls on the source from other threads do not wait for the placement: it holds the handle's lock only
+ * while it reads what the handle describes.  The tree leaves HBM only for host_out.  sdfhip_scene_combine, _prune, _edit, _mesh and
+ * the renderers take the result as any other scene.  The rule, pinned (fp32, each operation rounded on its own in the order written;
+ * S = 2^-d the edge of a cell of depth d):
+ *   inverse map      for a destination point p: d = p - t per axis; inv = 1.0f / s;
+ *                    q_a = ((R[0][a] * d_0 + R[1][a] * d_1) + R[2][a] * d_2) * inv -- the transpose of R applied to d
+ *   value            qc = min(max(q, 0), 1) per axis (fmaxf / fminf); e = q - qc; D = the distance sdfhip_scene_sample returns at qc
+ *                    (find from the root, interpol_world: the shader's arithmetic untouched);
+ *                    value(p) = (D + sqrtf((e_0 * e_0 + e_1 * e_1) + e_2 * e_2)) * s.  Inside the source's cube e is 0 and the value is
+ *                    D * s, with no branch; outside, the source's field continues at slope 1 from the nearest point of the cube's surface
+ *   tree             sdfhip_trimesh_build's construct rule with this value: corner k of a node of depth d with integer coordinates c
+ *                    sits at (c + split(k)) * S, its centre at (2 c + 1) * (S * 0.5f) (exact dyadics); byte = FromFloat(value, S); the
+ *                    node splits iff fabsf(value(centre)) < 2 * S && d < depth.  Every point is evaluated as if alone: that siblings
+ *                    share corners is an optimisation that cannot change a byte
+ *   node order       breadth first, as sdfhip_trimesh_build's and sdfhip_scene_combine's: node 0 is the root (parent -1); a level's
+ *                    blocks of eight follow in ascending index of their parents; child i is at block + i; a leaf's children field is
+ *                    -1.  Bytes and links depend on the source's arrays and the placement alone, never on which wave finished first
+ * What the rule implies.  A source's bytes saturate at -0.5 and 1.5 of its leaf's edge, so |D| stays small where the source's leaves
+ * are small: inside a solid and in the band round it the result can be finer than the source, by up to two levels of the scaled
+ * leaf.  Nothing is pruned: sdfhip_scene_prune removes what a tolerance allows.  The identity placement is a resampling, not a clone
+ * (the depth-4 sphere of 3 465 nodes comes back with 4 681).  A source moved wholly out of the cube, or depth 0, gives the root alone.
+ * placement: the caller sets size = sizeof(sdfhip_placement); the struct grows like sdfhip_prune_options (a larger, newer struct is
+ * accepted when the fields this library does not know are all -1).  There is no _default helper.  rotation: R, row-major, orthogonal
+ * (mirrors allowed); scale: s > 0; translation: t; depth: -1 = the source's depth, else 0..12 -- the deepest level of the result.
+ * out, host_out: either may be NULL, not both; host_out: the result's host arrays (release with sdfhip_octdata_free).  stats (may be
+ * NULL): samples counts the source look-ups, 9 for the root and 35 for every block of eight siblings (the 27 corners of its lattice and
+ * its 8 centres).
+ * SDFHIP_ERR_ARG: a null scene or placement, both outputs NULL, a size the growth rule refuses, a non-finite field, s <= 0, a rotation
+ * with max |(R R^T - I)_ij| > 1e-4 (computed in double; the bound defines the interface), depth outside -1..12 -- each of these before
+ * any device call -- and a result of more than 2^31 - 1 nodes; SDFHIP_ERR_BAD_TREE: depth -1 on a source that has no depth to give (not
+ * consistent, or deeper than 12 levels; with a depth given the call accepts every scene sdfhip_scene_sample accepts); SDFHIP_ERR_NOMEM:
+ * out of device memory (the input stays valid, nothing leaks).
+ * A look-up is a grid lookup wherever the handle has a full-depth grid, as sdfhip_scene_raycast's, else the walk along the links;
+ * both give the same bytes.  Work is proportional to the result; its device memory grows level by level; the host waits once per
+ * level for the level's count; the new handle builds its lookup grids anew. */
+typedef struct sdfhip_placement {
+    uint32_t size;            /* sizeof(sdfhip_placement) of the caller's header */
+    float rotation[3][3];     /* R, row-major, orthogonal */
+    float scale;              /* s > 0 */
+    float translation[3];     /* t */
+    int32_t depth;            /* -1 = the source's depth; else 0..12 */
+} sdfhip_placement;           /* 60 bytes */
+typedef struct sdfhip_place_stats {
+    uint32_t nodes_in, nodes_out, depth_out, levels;
+    uint64_t samples;        /* source look-ups made */
+    float kernel_ms;         /* HIP events around the placement's kernels (the per-level host synchronisations included) */
+    float scene_ms;          /* building the new handle (fused records, lookup grids), host clock */
+    float total_ms;          /* host clock, the whole call */
+    uint32_t pad_;
+} sdfhip_place_stats;        /* 40 bytes */
+SDFHIP_API int sdfhip_scene_place(sdfhip_scene *scene, const sdfhip_placement *pl, sdfhip_scene **out, sdfhip_octdata *host_out,
+                                  sdfhip_place_stats *stats);
 
 /* ---- point and ray queries: what a resident scene answers without drawing a frame -------------------
  * Replaces: nothing in the reference's code -- its only consumer of the tree is Compute.hlsl; a host that wants the distance at a

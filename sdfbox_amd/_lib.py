@@ -51,7 +51,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -191,6 +191,32 @@ else:
     assert (ctypes.sizeof(CombineOptions), ctypes.sizeof(CombineStats)) == (8, 32)
 
 
+    class Placement(ctypes.Structure):
+        """sdfhip_placement: a source point x lands at scale * rotation @ x + translation.  rotation (3, 3) row-major, orthogonal;
+        scale > 0; depth None = the source's depth, else 0..12."""
+        _fields_ = [("size", ctypes.c_uint32), ("rotation", (ctypes.c_float * 3) * 3), ("scale", ctypes.c_float),
+                    ("translation", ctypes.c_float * 3), ("depth", ctypes.c_int32)]
+
+        def __init__(self, rotation=((1, 0, 0), (0, 1, 0), (0, 0, 1)), scale=1.0, translation=(0, 0, 0), depth=None):
+            rows = [[float(x) for x in row] for row in rotation]
+            if len(rows) != 3 or any(len(row) != 3 for row in rows):
+                raise ValueError("rotation must be 3 x 3")
+            t = [float(x) for x in translation]
+            if len(t) != 3:
+                raise ValueError("translation must have three components")
+            super().__init__(ctypes.sizeof(type(self)), ((ctypes.c_float * 3) * 3)(*[(ctypes.c_float * 3)(*row) for row in rows]), float(scale),
+                             (ctypes.c_float * 3)(*t), -1 if depth is None else int(depth))
+
+
+    class PlaceStats(ctypes.Structure):
+        _fields_ = [("nodes_in", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32), ("levels", ctypes.c_uint32),
+                    ("samples", ctypes.c_uint64), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
+                    ("pad_", ctypes.c_uint32)]
+
+
+    assert (ctypes.sizeof(Placement), ctypes.sizeof(PlaceStats)) == (60, 40)
+
+
     class Probe(ctypes.Structure):
         """sdfhip_probe: the answer for one point of sdfhip_scene_sample."""
         _fields_ = [("distance", ctypes.c_float), ("node", ctypes.c_uint32), ("scale", ctypes.c_float), ("status", ctypes.c_uint32),
@@ -317,6 +343,7 @@ _SIG = {
                                      _c.POINTER(EditStats)]),
     "sdfhip_scene_prune": (_c.c_int, [_vp, _c.POINTER(PruneOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PruneStats)]),
     "sdfhip_scene_combine": (_c.c_int, [_vp, _vp, _c.c_int32, _c.POINTER(CombineOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(CombineStats)]),
+    "sdfhip_scene_place": (_c.c_int, [_vp, _c.POINTER(Placement), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PlaceStats)]),
     "sdfhip_scene_sample": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
     "sdfhip_scene_sample_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),

@@ -65,6 +65,20 @@ def _rays(origins, dirs):
     return rays
 
 
+def placement(yaw, pitch, roll, scale=1.0, about=(0.5, 0.5, 0.5), to=(0.5, 0.5, 0.5)):
+    """(R, s, t) for Scene.Place from angles in degrees: R = Ry(yaw) @ Rx(pitch) @ Rz(roll) (right-handed, each about the named
+    axis), s = scale, and t such that the source point `about` lands at `to`: t = to - s R about.  Computed in double from the
+    arguments and rounded to float32 once, at the end."""
+    y, p, r = (np.deg2rad(float(a)) for a in (yaw, pitch, roll))
+    Ry = np.array([[np.cos(y), 0.0, np.sin(y)], [0.0, 1.0, 0.0], [-np.sin(y), 0.0, np.cos(y)]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(p), -np.sin(p)], [0.0, np.sin(p), np.cos(p)]])
+    Rz = np.array([[np.cos(r), -np.sin(r), 0.0], [np.sin(r), np.cos(r), 0.0], [0.0, 0.0, 1.0]])
+    R = Ry @ Rx @ Rz
+    s = float(scale)
+    t = np.asarray(to, dtype=np.float64).reshape(3) - s * (R @ np.asarray(about, dtype=np.float64).reshape(3))
+    return R.astype(np.float32), np.float32(s), t.astype(np.float32)
+
+
 class Scene:
     """A scene resident in one GPU's HBM (replaces the `data` / `values`
     bindings of Program.cs:147-152)."""
@@ -176,6 +190,28 @@ class Scene:
         st = _lib.CombineStats()
         check(lib.sdfhip_scene_combine(self._h, other._h, int(op), ctypes.byref(opt), ctypes.byref(res._h),
                                        ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def Place(self, rotation, scale, translation, depth=None, want_octdata=False, want_stats=False):
+        """Placement (sdfhip_scene_place): this scene resampled under p = scale * rotation @ x + translation -- rotation (3, 3)
+        row-major and orthogonal (a mirror is allowed), scale > 0; placement() makes the three from angles -- into a NEW Scene in
+        breadth-first order on the same device; this one is left as it was.  depth: None = this tree's depth, else 0..12.  Nothing is
+        pruned (chain Prune), and the identity is a resampling, not a clone.  want_octdata: also the result's host arrays;
+        want_stats: a PlaceStats."""
+        from .octdata import OctData
+        pl = _lib.Placement(np.asarray(rotation, dtype=np.float32).reshape(3, 3).tolist(), scale, np.asarray(translation, dtype=np.float32).reshape(3).tolist(), depth)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = self.device
+        raw = _lib.COctData()
+        st = _lib.PlaceStats()
+        check(lib.sdfhip_scene_place(self._h, ctypes.byref(pl), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
         res._describe()
         out = [res]
         if want_octdata:
