@@ -754,6 +754,63 @@ SDFHIP_API void sdfhip_mesh_free(sdfhip_mesh *mesh);
 SDFHIP_API int sdfhip_mesh_save_ply(const sdfhip_mesh *mesh, const char *path);
 SDFHIP_API int sdfhip_mesh_save_obj(const sdfhip_mesh *mesh, const char *path);
 
+/* ---- the measure: volume, area, moments and bounds of a resident scene --------------------------------
+ * Replaces: nothing in the reference's code -- its tree only ever becomes pixels, and no call there says anything quantitative about
+ * the solid it describes.  sdfhip_scene_measure returns the volume, the surface area, the first and second moments about the origin
+ * and the tight bounding box of the solid that N7's mesh bounds (marching tetrahedra on the Kuhn decomposition, the surface at byte
+ * 63.75): what a placement fits from (sdfbox_amd.placement_fit), what an edit, a combination or a prune at a tolerance changed, and
+ * the mass properties (centroid = moment1 / volume; inertia by the parallel-axis theorem) of a simulation's body at unit density.
+ * It measures the solid the BYTES describe and the renderer draws, not the shape the builder was given: inside bytes saturate at -0.5
+ * of a leaf's edge, which pulls the interpolated surface inward -- the depth-4 sphere of radius 0.3 (tests/golden/sphere_d4.asdf)
+ * measures 0.10884054856 against the ball's 0.11309734, 3.76 % short, its mesh's vertices at radii 0.277 .. 0.3008.
+ * The rule, pinned (fp64, each operation rounded on its own in the order written; DESIGN.md section 8 has it with the GPU path):
+ *   cells      N7's: level -1 the leaves, level L the leaves of depth <= L and the internal nodes of depth exactly L; a corner is inside
+ *              iff its byte <= 63; integer coordinates c of the cell's depth d from the links; S = 2^-d; cube corner k lies at
+ *              ((double)c_a + bit_a(k)) * S.  A cell with no inside corner contributes +0.0 to every sum and nothing to the bounds
+ *   cut point  on a tetrahedron's edge between local corners lo < hi (cube corners whose bits nest): t = (63.75 - b_lo) / (b_hi - b_lo),
+ *              per axis ((double)(c_a + bit_a(lo)) + (bit_a(hi) != bit_a(lo) ? t : 0.0)) * S -- N7's vertex in fp64
+ *   full cell  all eight bytes <= 63: the box lo = c * S, hi = (c + 1) * S: V = (S*S)*S, mid_a = (lo_a + hi_a) * 0.5, m1_a = V * mid_a,
+ *              m2_aa = V * (((lo_a*lo_a + lo_a*hi_a) + hi_a*hi_a) / 3.0), m2_ab = V * (mid_a * mid_b), area 0
+ *   cut cell   mixed bytes: cell-local sums from +0.0 over N7's six tetrahedra in order, each with corners (0, v1, v2, 7), inside
+ *              corners i0 < i1 < .. and outside corners o0 < o1 < .., P(i, o) the cut point of that edge:
+ *                four inside   the tetrahedron itself
+ *                one           (i0, P(i0,o0), P(i0,o1), P(i0,o2))
+ *                three         the whole tetrahedron added, then (o0, P(i0,o0), P(i1,o0), P(i2,o0)) subtracted
+ *                two           q0 = P(i0,o0), q1 = P(i0,o1), q2 = P(i1,o1), q3 = P(i1,o0): (i0,q0,q1,q2), (i0,q0,q3,q2), (i0,i1,q3,q2) -- the
+ *                              prism between the triangles (i0,q0,q1) and (i1,q3,q2)
+ *   tetrahedron (a, b, c, d): e1 = b-a, e2 = c-a, e3 = d-a; det = (e1x*(e2y*e3z - e2z*e3y) - e1y*(e2x*e3z - e2z*e3x)) + e1z*(e2x*e3y - e2y*e3x);
+ *              V = fabs(det) / 6.0; s = ((a+b)+c)+d; volume += V; m1_a += (V*0.25) * s_a;
+ *              m2_ij += (V*0.05) * ((((a_i*a_j + b_i*b_j) + c_i*c_j) + d_i*d_j) + s_i*s_j)   (subtracted: -= each)
+ *   area       N7's triangles (p0, p1, p2) of that tetrahedron and mask, vertices in fp64 in the table's order: u = p1-p0, v = p2-p0,
+ *              n = (uy*vz - uz*vy, uz*vx - ux*vz, ux*vy - uy*vx), n2 = (nx*nx + ny*ny) + nz*nz, area += 0.5 * (double)sqrtf((float)n2) --
+ *              the root in fp32 on purpose (the one root N11 already holds equal to numpy on the GPU; 6e-8 relative per triangle
+ *              against a discretisation error of 1e-3).  Each cell's own triangles, as the mesh: no crack patching
+ *   bounds     minimum and maximum per axis over the box corners of full cells, the inside cube corners of cut cells and their cut
+ *              points: exact, whatever the order.  +inf / -inf when the solid is empty
+ *   sums       each of the eleven (volume, area, moment1[3], moment2[6]) is the adjacent-pair tree over NODE INDEX: x[i] = node i's
+ *              contribution (+0.0 for a node that is no cell), padded with +0.0 to a power of two, x = x[0::2] + x[1::2] until one value
+ *              is left -- the bits never depend on which wave finished first, and no double is added atomically.  They do depend on
+ *              the node order: the same tree in another order agrees to rounding (1e-12 relative), not bit for bit
+ * The call is synchronous, on the scene's own stream, under the handle's lock as sdfhip_scene_mesh; the scene is untouched and frames
+ * enqueued on other streams run beside it.  opt: NULL = level -1; the struct grows like sdfhip_mesh_options.
+ * SDFHIP_ERR_ARG: a null scene or output, level outside -1..12, an options struct the size rules refuse (all before any device call);
+ * SDFHIP_ERR_BAD_TREE: the tree is not consistent (stack_kernel_ok == 0) or deeper than 12 levels; SDFHIP_ERR_NOMEM: out of device
+ * memory (136 bytes per 1024 nodes; nothing leaks).  *out is zeroed on every failure. */
+typedef struct sdfhip_measure_options { uint32_t size; int32_t level; } sdfhip_measure_options;   /* level: as sdfhip_mesh_options */
+typedef struct sdfhip_measure {
+    double volume, area;
+    double moment1[3];                      /* integral of x, y, z over the solid */
+    double moment2[6];                      /* integral of xx, yy, zz, xy, xz, yz, about the origin */
+    double bounds_min[3], bounds_max[3];    /* tight box of the solid; +inf / -inf when it is empty */
+    uint32_t nodes, depth;                  /* the scene's */
+    uint32_t cells, cells_cut, cells_inside;/* the level's cells; those with mixed bytes; those with all eight bytes <= 63 */
+    uint32_t cells_at_depth[13];            /* the level's cells by depth */
+    float kernel_ms;                        /* HIP events around the kernels */
+    float total_ms;                         /* host clock, the whole call */
+} sdfhip_measure;
+SDFHIP_API void sdfhip_measure_options_default(sdfhip_measure_options *opt);
+SDFHIP_API int sdfhip_scene_measure(sdfhip_scene *scene, const sdfhip_measure_options *opt, sdfhip_measure *out);
+
 /* ---- triangle mesh -> ASDF: exact signed distance on the GPU ------------------------------------------
  * Replaces: nothing in the live reference -- SdfGen builds from the nearest POINT of a cloud (dllmain.cpp:117-161), which
  * sdfhip_sdfgen restates.  It is the intent of the reference's abandoned per-triangle GPU generator (SdfBox/GpuGenerator.cs +

@@ -51,7 +51,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Hit, Info, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -254,6 +254,50 @@ else:
                     ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
 
 
+    class MeasureOptions(ctypes.Structure):
+        """sdfhip_measure_options: level as MeshOptions"""
+        _fields_ = [("size", ctypes.c_uint32), ("level", ctypes.c_int32)]
+
+        def __init__(self, level=-1):
+            super().__init__(ctypes.sizeof(type(self)), int(level))
+
+
+    class Measure(ctypes.Structure):
+        """sdfhip_measure: volume, area, first and second moments about the origin, the tight bounds and the cell counts of the solid a
+        scene describes (Scene.Measure) -- the solid the bytes describe and the renderer draws."""
+        _fields_ = [("volume", ctypes.c_double), ("area", ctypes.c_double), ("moment1", ctypes.c_double * 3), ("moment2", ctypes.c_double * 6),
+                    ("bounds_min", ctypes.c_double * 3), ("bounds_max", ctypes.c_double * 3), ("nodes", ctypes.c_uint32), ("depth", ctypes.c_uint32),
+                    ("cells", ctypes.c_uint32), ("cells_cut", ctypes.c_uint32), ("cells_inside", ctypes.c_uint32),
+                    ("cells_at_depth", ctypes.c_uint32 * 13), ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+        @property
+        def empty(self):
+            return not self.volume > 0.0
+
+        @property
+        def centroid(self):
+            """moment1 / volume as three floats, or None for an empty solid"""
+            if self.empty:
+                return None
+            return tuple(m / self.volume for m in self.moment1)
+
+        def inertia(self):
+            """The 3 x 3 inertia tensor about the centroid at unit density (nested tuples, rows x y z): the second moments about the
+            origin moved to the centroid by the parallel-axis theorem, then I_aa = the other two central moments' sum, I_ab = -the
+            central product.  None for an empty solid."""
+            if self.empty:
+                return None
+            V = self.volume
+            c = self.centroid
+            xx, yy, zz, xy, xz, yz = self.moment2
+            cxx, cyy, czz = xx - V * c[0] * c[0], yy - V * c[1] * c[1], zz - V * c[2] * c[2]
+            cxy, cxz, cyz = xy - V * c[0] * c[1], xz - V * c[0] * c[2], yz - V * c[1] * c[2]
+            return ((cyy + czz, -cxy, -cxz), (-cxy, cxx + czz, -cyz), (-cxz, -cyz, cxx + cyy))
+
+
+    assert (ctypes.sizeof(MeasureOptions), ctypes.sizeof(Measure)) == (8, 216)
+
+
     class TriMeshOptions(ctypes.Structure):
         """sdfhip_trimesh_options: fit 0 = coordinates as given, 1 = bounding box centred at 0.5 with its longest side `fill` (None = default)."""
         _fields_ = [("size", ctypes.c_uint32), ("fit", ctypes.c_int32), ("fill", ctypes.c_float)]
@@ -353,6 +397,8 @@ _SIG = {
     "sdfhip_scene_mesh": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _c.POINTER(CMesh), _c.POINTER(MeshStats)]),
     "sdfhip_scene_mesh_device": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp]),
     "sdfhip_mesh_free": (None, [_c.POINTER(CMesh)]),
+    "sdfhip_measure_options_default": (None, [_c.POINTER(MeasureOptions)]),
+    "sdfhip_scene_measure": (_c.c_int, [_vp, _c.POINTER(MeasureOptions), _c.POINTER(Measure)]),
     "sdfhip_mesh_save_ply": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
     "sdfhip_mesh_save_obj": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
     "sdfhip_load_ply_mesh": (_c.c_int, [_c.c_char_p, _c.POINTER(CMesh)]),

@@ -1,6 +1,6 @@
 // Surface extraction from a resident scene (gfx950): marching tetrahedra on the Kuhn decomposition of every cell whose bytes are
-// mixed, as a triangle soup of {position, normal} vertices in a pinned order.  Non-template helpers and three kernels: included by
-// mesh.hip ONLY.  Host side, C ABI: mesh.hip; the writers: mesh_io.cpp.
+// mixed, as a triangle soup of {position, normal} vertices in a pinned order.  Non-template helpers (the cells and their tetrahedra:
+// cell_tets.h) and three kernels: included by mesh.hip ONLY.  Host side, C ABI: mesh.hip; the writers: mesh_io.cpp.
 //
 // Replaces: nothing in the reference's code -- its tree only ever becomes pixels.
 //
@@ -19,7 +19,7 @@
 // Reading the records twice (2 x 16 bytes per node) is cheaper than a per-node count array written, scanned and read back, and
 // keeps the temporary memory at four bytes per 1024 nodes.
 #pragma once
-#include "raymarch_device.h"
+#include "cell_tets.h"      // the cells, their tetrahedra and triangles (shared with measure_kernels.h)
 #include "scan_device.h"     // block_exclusive_scan
 
 namespace sdfhip {
@@ -27,81 +27,10 @@ namespace sdfhip {
 constexpr int MESH_THREADS = 256;
 constexpr int MESH_ROWS = 4;                                  // rows of MESH_THREADS consecutive nodes per workgroup
 constexpr uint32_t MESH_CHUNK = MESH_THREADS * MESH_ROWS;
-constexpr int MESH_MAX_DEPTH = LM;                            // the deepest tree the walk is sized for (checked by the host side)
 
 // what the passes count beside the triangles: 64-bit triangle total (k_mesh_scan), cells of the level, cells whose bytes are mixed
 struct MeshHeader { unsigned long long n_triangles; uint32_t cells, cells_cut; };
 
-// The six tetrahedra round the diagonal 0-7, one per axis permutation in lexicographic order: corners {0, v1, v2, 7} with
-// v1 = 1 << a0, v2 = v1 | 1 << a1.  Packed four bits per local corner.
-__device__ __forceinline__ uint32_t tet_corners(int t)
-{
-    // (x,y,z) 0137  (x,z,y) 0157  (y,x,z) 0237  (y,z,x) 0267  (z,x,y) 0457  (z,y,x) 0467
-    const uint32_t v1 = 0x442211u, v2 = 0x656353u;
-    return 0x7000u | (((v2 >> (4 * t)) & 7u) << 8) | (((v1 >> (4 * t)) & 7u) << 4);
-}
-
-// The triangles of (tetrahedron, inside mask): bits 0-1 their number; vertex k of the (up to) six at bits 4 + 4k: the cut edge's
-// local corners i (bits 0-1) < j (bits 2-3).  Cut edges in ascending (i, j) order for one or three inside corners, the quad
-// (i0,o0) (i0,o1) (i1,o1) (i1,o0) split along its first diagonal for two; the last two vertices of a triangle swapped where the
-// orientation test on the unit tetrahedron with cuts at the edge midpoints asks for it (counter-clockwise seen from outside:
-// dot(cross(p1 - p0, p2 - p0), mean(outside corners) - mean(inside corners)) > 0).  Worked out once from that rule; the
-// restatement derives its own and the GPU tests compare the vertices.
-static __device__ const uint32_t MESH_TRIANGLES[6 * 16] = {
-    0x0000000u, 0x000c841u, 0x0009d41u, 0x9d8dc82u, 0x000e981u, 0xe94ce42u, 0x8e4ed42u, 0x000edc1u, 0x000dec1u, 0xde4e842u, 0xec49e42u, 0x0009e81u, 0xcd8d982u, 0x000d941u, 0x0008c41u, 0x0000000u,
-    0x0000000u, 0x0008c41u, 0x000d941u, 0xd98cd82u, 0x0009e81u, 0x9e4ec42u, 0xe84de42u, 0x000dec1u, 0x000edc1u, 0xed48e42u, 0xce4e942u, 0x000e981u, 0xdc89d82u, 0x0009d41u, 0x000c841u, 0x0000000u,
-    0x0000000u, 0x0008c41u, 0x000d941u, 0xd98cd82u, 0x0009e81u, 0x9e4ec42u, 0xe84de42u, 0x000dec1u, 0x000edc1u, 0xed48e42u, 0xce4e942u, 0x000e981u, 0xdc89d82u, 0x0009d41u, 0x000c841u, 0x0000000u,
-    0x0000000u, 0x000c841u, 0x0009d41u, 0x9d8dc82u, 0x000e981u, 0xe94ce42u, 0x8e4ed42u, 0x000edc1u, 0x000dec1u, 0xde4e842u, 0xec49e42u, 0x0009e81u, 0xcd8d982u, 0x000d941u, 0x0008c41u, 0x0000000u,
-    0x0000000u, 0x000c841u, 0x0009d41u, 0x9d8dc82u, 0x000e981u, 0xe94ce42u, 0x8e4ed42u, 0x000edc1u, 0x000dec1u, 0xde4e842u, 0xec49e42u, 0x0009e81u, 0xcd8d982u, 0x000d941u, 0x0008c41u, 0x0000000u,
-    0x0000000u, 0x0008c41u, 0x000d941u, 0xd98cd82u, 0x0009e81u, 0x9e4ec42u, 0xe84de42u, 0x000dec1u, 0x000edc1u, 0xed48e42u, 0xce4e942u, 0x000e981u, 0xdc89d82u, 0x0009d41u, 0x000c841u, 0x0000000u,
-};
-
-// bit k: corner k is inside (byte <= 63; the surface is at 63.75, which no byte equals)
-__device__ __forceinline__ uint32_t inside_bits(uint32_t v0, uint32_t v1)
-{
-    uint32_t m = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        m |= (((v0 >> (8 * k)) & 0xFFu) <= 63u ? 1u : 0u) << k;
-        m |= (((v1 >> (8 * k)) & 0xFFu) <= 63u ? 1u : 0u) << (4 + k);
-    }
-    return m;
-}
-// the four inside bits of tetrahedron t's local corners
-__device__ __forceinline__ uint32_t tet_mask(uint32_t in8, int t)
-{
-    const uint32_t c = tet_corners(t);
-    return (in8 & 1u) | (((in8 >> ((c >> 4) & 7u)) & 1u) << 1) | (((in8 >> ((c >> 8) & 7u)) & 1u) << 2) | (((in8 >> 7) & 1u) << 3);
-}
-// triangles of a cell with these inside bits: per tetrahedron 1 for one or three inside corners, 2 for two
-__device__ __forceinline__ uint32_t cell_triangles(uint32_t in8)
-{
-    uint32_t n = 0;
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        const uint32_t pc = (uint32_t)__popc(tet_mask(in8, t));
-        n += pc == 2u ? 2u : (pc & 1u);
-    }
-    return n;
-}
-
-// depth of node i: the links up to the root (mixed nodes of a level >= 0 pass only)
-__device__ __forceinline__ int node_depth(const NodeRec *__restrict__ nodes, uint32_t n, int32_t parent)
-{
-    int d = 0;
-    while (parent >= 0 && (uint32_t)parent < n && d <= MESH_MAX_DEPTH) {
-        parent = (int32_t)nodes[parent].x;
-        d++;
-    }
-    return d;
-}
-
-// is node (children, depth) a cell of `level`: -1 = the leaves; L = the leaves of depth <= L and the internal nodes of depth L
-__device__ __forceinline__ bool is_cell(int32_t children, int level, int depth)
-{
-    const bool leaf = children < 0;
-    return level < 0 ? leaf : (leaf ? depth <= level : depth == level);
-}
 
 // A node's triangle count, and whether it is a cell and a cut one (for the statistics)
 __device__ __forceinline__ uint32_t node_triangles(const NodeRec *__restrict__ nodes, uint32_t n, const NodeRec &r, int level, bool &cell, bool &cut)

@@ -79,6 +79,21 @@ def placement(yaw, pitch, roll, scale=1.0, about=(0.5, 0.5, 0.5), to=(0.5, 0.5, 
     return R.astype(np.float32), np.float32(s), t.astype(np.float32)
 
 
+def placement_fit(measure, yaw=0, pitch=0, roll=0, size=0.8, to=(0.5, 0.5, 0.5)):
+    """(R, s, t) for Scene.Place that fits a measured solid: the centre of `measure`'s bounds (a Scene.Measure result, or anything
+    with bounds_min and bounds_max) lands at `to`, and the longest side of those bounds becomes `size`; the angles are placement()'s.
+    The bounds are the source's own, axis-aligned before the rotation: a rotated box's own bounds are larger.  Raises ValueError on
+    an empty solid (bounds +inf / -inf) and on one without extent."""
+    lo = np.array([float(x) for x in measure.bounds_min], dtype=np.float64)
+    hi = np.array([float(x) for x in measure.bounds_max], dtype=np.float64)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (hi < lo).any():
+        raise ValueError("placement_fit: the measured solid is empty")
+    side = float((hi - lo).max())
+    if not side > 0.0:
+        raise ValueError("placement_fit: the measured solid has no extent")
+    return placement(yaw, pitch, roll, float(size) / side, about=(lo + hi) * 0.5, to=to)
+
+
 class Scene:
     """A scene resident in one GPU's HBM (replaces the `data` / `values`
     bindings of Program.cs:147-152)."""
@@ -282,6 +297,17 @@ class Scene:
         check(lib.sdfhip_scene_mesh_device(self._h, ctypes.byref(opt), ctypes.c_void_p(int(out_ptr)) if out_ptr else None, int(capacity),
                                            ctypes.byref(n), ctypes.c_void_p(int(stream)) if stream else None))
         return n.value
+
+    # -- the measure (sdfhip_scene_measure): what the solid amounts to -----------------------------------------------------------
+    def Measure(self, level=-1):
+        """Volume, area, first and second moments about the origin, the tight bounds and the cell counts of the solid this scene
+        describes -- the one Mesh bounds and the renderer draws, in double precision: a _lib.Measure with the raw fields of
+        sdfhip_measure, `centroid` (None for an empty solid) and `inertia()`.  level: as Mesh.  The sums are the same bits on every
+        call; placement_fit() makes a placement from the bounds."""
+        opt = _lib.MeasureOptions(level)
+        out = _lib.Measure()
+        check(lib.sdfhip_scene_measure(self._h, ctypes.byref(opt), ctypes.byref(out)))
+        return out
 
     def close(self):
         if self._h:
