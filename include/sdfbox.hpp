@@ -237,6 +237,27 @@ public:
         sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Exact distance (sdfhip_scene_distance / sdfhip_scene_offset; nothing in the reference corresponds).  Distance: how far points
+    // (xyz: 3 floats per point) are from the loaded model's surface -- the triangles of its mesh at `level` -- at any range, where
+    // Sample's distance saturates a leaf edge away; a bad element gets SDFHIP_QUERY_INVALID, not an exception.  Offset: the model grown
+    // by delta (shrunk when it is negative); Shell: the wall of `thickness` > 0 centred on its surface -- each a new tree of at most
+    // `depth` levels (-1 = the model's own depth, else 0..12), which replaces the loaded model as Place's result does.  Nothing is
+    // pruned (chain Prune).  host_out (may be null): the result's host arrays
+    std::vector<sdfhip_clearance> Distance(const std::vector<float> &xyz, int level = -1)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Distance: no model loaded");
+        std::vector<sdfhip_clearance> out(xyz.size() / 3);
+        Check(sdfhip_scene_distance(scene, xyz.data(), (uint32_t)out.size(), level, out.data()));
+        return out;
+    }
+    void Offset(float delta, int depth = -1, int level = -1, sdfhip_offset_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        OffsetAs(SDFHIP_OFFSET_GROW, delta, depth, level, stats, host_out, "Offset: no model loaded");
+    }
+    void Shell(float thickness, int depth = -1, int level = -1, sdfhip_offset_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        OffsetAs(SDFHIP_OFFSET_SHELL, thickness, depth, level, stats, host_out, "Shell: no model loaded");
+    }
     // Point and ray queries (sdfhip_scene_sample / _raycast / _pick; nothing in the reference corresponds): what the loaded model
     // answers without drawing a frame, with the shader's own arithmetic.  Sample: distance, cell and gradient at points (xyz: 3 floats
     // per point); Raycast: the primary march of Compute.hlsl:194-203 for arbitrary rays; Pick: that march for pixels {x, y} of the
@@ -323,6 +344,21 @@ public:
     }
 
 private:
+    void OffsetAs(int32_t mode, float amount, int depth, int level, sdfhip_offset_stats *stats, sdfhip_octdata *host_out, const char *unloaded)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, unloaded);
+        sdfhip_offset_options opt = {};
+        opt.size = (uint32_t)sizeof(sdfhip_offset_options);
+        opt.mode = mode;
+        opt.amount = amount;
+        opt.depth = depth;
+        opt.level = level;
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_offset(scene, &opt, &fresh, host_out, stats));
+        sdfhip_scene_free(scene);
+        scene = fresh;
+    }
+
     int device;
     sdfhip_scene *scene = nullptr;
 };

@@ -811,6 +811,83 @@ typedef struct sdfhip_measure {
 SDFHIP_API void sdfhip_measure_options_default(sdfhip_measure_options *opt);
 SDFHIP_API int sdfhip_scene_measure(sdfhip_scene *scene, const sdfhip_measure_options *opt, sdfhip_measure *out);
 
+/* ---- exact distance: clearance query, offset and shell ------------------------------------------------
+ * Replaces: nothing in the reference's code -- its field is only ever read as stored, and the stored field is a distance only in a
+ * thin band round the surface: a leaf of edge S holds values in [-0.5 S, 1.5 S] and every leaf away from the surface is saturated (the
+ * notes at sdfhip_scene_place and sdfhip_scene_measure).  sdfhip_scene_sample therefore cannot say how far a point is from the model
+ * beyond one leaf edge, and a scene could not be grown, shrunk or hollowed.  These calls compute the exact distance from a point to
+ * the surface the scene describes, at any range, and build two modelling operations on it.  The rule, pinned (fp32, each operation
+ * rounded on its own in the order written; S = 2^-d the edge of a cell of depth d):
+ *   surface(scene, level)  the triangles sdfhip_scene_mesh emits for `level` (-1 = full detail, else as sdfhip_mesh_options): each the
+ *                    three emitted positions a, b, c in emitted order.  Normals play no part
+ *   d2(p)            best = +inf; for every triangle t = D(a, b, c, p), sdfhip_trimesh_build's squared distance below (it reads the
+ *                    nine position floats only), then best = t < best ? t : best -- a NaN from a degenerate triangle never wins.  The
+ *                    minimum of a set of floats does not depend on the order: d2 depends on the scene's arrays and p alone, never on
+ *                    the traversal or on which wave finished first.  An empty surface gives +inf
+ *   sign(p)          negative iff the distance sdfhip_scene_sample returns at pc = min(max(p, 0), 1) per axis (fmaxf / fminf, as the
+ *                    placement clamps) is < 0.0f: find from the root and interpol_world, untouched.  The trilinear zero set of that
+ *                    distance and the tetrahedra-linear surface the triangles bound differ by a sliver next to the surface; a point
+ *                    inside the sliver gets the other sign, and since sqrtf(d2) there is no larger than the sliver is wide, dist is
+ *                    off by at most twice that width (a fraction of the cell's edge), and only there
+ *   dist(p)          sign(p) * sqrtf(d2(p))
+ *   value(p)         SDFHIP_OFFSET_GROW: dist(p) - amount (amount > 0 grows the solid, < 0 shrinks it);
+ *                    SDFHIP_OFFSET_SHELL: fabsf(dist(p)) - amount * 0.5f (amount > 0: the wall of that thickness centred on the surface)
+ *   tree             sdfhip_scene_place's, word for word, with this value: byte = FromFloat(value, S); a node splits iff
+ *                    fabsf(value(centre)) < 2 * S && d < depth; breadth-first node order; every point evaluated as if alone.  An empty
+ *                    surface (value +-inf) gives the root alone.  Nothing is pruned: chain sdfhip_scene_prune
+ * sdfhip_scene_distance answers n points (xyz: n x 3 floats, packed) with n sdfhip_clearance records; the _device form takes device
+ * pointers, launches on the caller's stream and returns, as sdfhip_scene_sample_device.  A non-finite coordinate gets
+ * SDFHIP_QUERY_INVALID and zeros, and the rest of the batch is answered.  Of the triangles that tie on d2 the one lowest in the mesh's
+ * emitted order gives `node` and `nearest`; when d2 is +inf (an empty surface, or a point so far away that every squared distance
+ * overflows) both are zero.  `visited` counts the records the search loaded: it depends on the point and the scene alone, and is the
+ * same on every call.  level: -1, or 0..12.
+ * sdfhip_scene_offset builds the tree of value(p) as a NEW handle `*out` on the same device: the input is untouched (frames in flight
+ * on it included), either handle may be freed first, and the handle's lock is held only while its description is read.  opt: the
+ * caller sets size = sizeof(sdfhip_offset_options); the struct grows like sdfhip_prune_options (a larger, newer struct is accepted when
+ * the fields this library does not know are all -1).  depth: -1 = the source's depth, else 0..12; level: the source surface's level.
+ * out, host_out: either may be NULL, not both; host_out: the result's host arrays (release with sdfhip_octdata_free).  stats (may be
+ * NULL): points counts the evaluated points (9 for the root, 35 for every block of eight siblings), visited the records their
+ * searches loaded.
+ * SDFHIP_ERR_ARG: a null scene, options or point / record pointer (n > 0), both outputs NULL, a size the growth rule refuses, a
+ * non-finite amount, a shell's thickness <= 0, an unknown mode, depth or level outside -1..12 -- each before any device call -- and a
+ * result of more than 2^31 - 1 nodes; SDFHIP_ERR_BAD_TREE: a source sdfhip_scene_mesh refuses (not consistent, or deeper than 12
+ * levels); SDFHIP_ERR_NOMEM: out of device memory (the input stays valid, nothing leaks).
+ * The search (csrc/distance_kernels.h) is depth first from the root with the children of a node nearest first, skips a subtree that
+ * holds no cut cell (a bitmap over the nodes, rebuilt per call: 4 bytes per 32 nodes) or whose box cannot hold anything nearer than the
+ * best so far -- on a margin derived there for the rounding of the bound and of D, but for one case of D's face branch that DESIGN.md
+ * N13 names -- and recomputes a cut cell's triangles with the mesh's own arithmetic.  Work per point grows with the number of
+ * cells about as near as the nearest one. */
+enum { SDFHIP_OFFSET_GROW = 0, SDFHIP_OFFSET_SHELL = 1 };
+typedef struct sdfhip_clearance {   /* 32 bytes: the answer for one point */
+    float distance;                 /* dist(p): signed, not saturated */
+    uint32_t node;                  /* the cut cell that holds the nearest triangle */
+    float nearest[3];               /* the closest point q on that triangle: p - r of D */
+    uint32_t status;                /* SDFHIP_QUERY_HIT or SDFHIP_QUERY_INVALID; HIT with distance +-inf: an empty surface */
+    uint32_t visited;               /* records the search loaded: the work measure */
+    uint32_t pad_;
+} sdfhip_clearance;
+typedef struct sdfhip_offset_options {
+    uint32_t size;            /* sizeof(sdfhip_offset_options) of the caller's header */
+    int32_t mode;             /* SDFHIP_OFFSET_GROW or SDFHIP_OFFSET_SHELL */
+    float amount;             /* GROW: delta; SHELL: the thickness, > 0 */
+    int32_t depth;            /* -1 = the source's depth; else 0..12 */
+    int32_t level;            /* the source surface's level: -1 = full detail; else 0..12 */
+} sdfhip_offset_options;      /* 20 bytes */
+typedef struct sdfhip_offset_stats {
+    uint32_t nodes_in, nodes_out, depth_out, levels;
+    uint64_t points;         /* points evaluated */
+    uint64_t visited;        /* records their searches loaded */
+    float kernel_ms;         /* HIP events around the call's kernels (the per-level host synchronisations included) */
+    float scene_ms;          /* building the new handle (fused records, lookup grids), host clock */
+    float total_ms;          /* host clock, the whole call */
+    uint32_t pad_;
+} sdfhip_offset_stats;       /* 48 bytes */
+SDFHIP_API int sdfhip_scene_distance(sdfhip_scene *scene, const float *xyz, uint32_t n, int32_t level, sdfhip_clearance *out);
+SDFHIP_API int sdfhip_scene_distance_device(sdfhip_scene *scene, const float *d_xyz, uint32_t n, int32_t level, sdfhip_clearance *d_out,
+                                            void *stream);
+SDFHIP_API int sdfhip_scene_offset(sdfhip_scene *scene, const sdfhip_offset_options *opt, sdfhip_scene **out, sdfhip_octdata *host_out,
+                                   sdfhip_offset_stats *stats);
+
 /* ---- triangle mesh -> ASDF: exact signed distance on the GPU ------------------------------------------
  * Replaces: nothing in the live reference -- SdfGen builds from the nearest POINT of a cloud (dllmain.cpp:117-161), which
  * sdfhip_sdfgen restates.  It is the intent of the reference's abandoned per-triangle GPU generator (SdfBox/GpuGenerator.cs +

@@ -45,13 +45,14 @@ SHAPE_SPHERE, SHAPE_TORUS, SHAPE_GYROID = 0, 1, 2
 EDIT_CARVE, EDIT_ADD = 0, 1          # sdfhip_scene_edit: subtract / union
 BRUSH_SPHERE, BRUSH_BOX = 0, 1
 COMBINE_UNION, COMBINE_INTERSECT, COMBINE_SUBTRACT = 0, 1, 2      # sdfhip_scene_combine: A or B, A and B, A without B
+OFFSET_GROW, OFFSET_SHELL = 0, 1     # sdfhip_scene_offset: dist - amount / fabsf(dist) - amount / 2
 QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdfhip_probe.status / sdfhip_hit.status
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Clearance, OffsetOptions, OffsetStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -215,6 +216,31 @@ else:
 
 
     assert (ctypes.sizeof(Placement), ctypes.sizeof(PlaceStats)) == (60, 40)
+
+
+    class Clearance(ctypes.Structure):
+        """sdfhip_clearance: the answer for one point of sdfhip_scene_distance."""
+        _fields_ = [("distance", ctypes.c_float), ("node", ctypes.c_uint32), ("nearest", ctypes.c_float * 3), ("status", ctypes.c_uint32),
+                    ("visited", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+    class OffsetOptions(ctypes.Structure):
+        """sdfhip_offset_options: mode OFFSET_GROW (amount = delta) or OFFSET_SHELL (amount = the thickness, > 0); depth None = the
+        source's depth, else 0..12; level: the source surface's level, -1 = full detail."""
+        _fields_ = [("size", ctypes.c_uint32), ("mode", ctypes.c_int32), ("amount", ctypes.c_float), ("depth", ctypes.c_int32),
+                    ("level", ctypes.c_int32)]
+
+        def __init__(self, mode=0, amount=0.0, depth=None, level=-1):
+            super().__init__(ctypes.sizeof(type(self)), int(mode), float(amount), -1 if depth is None else int(depth), int(level))
+
+
+    class OffsetStats(ctypes.Structure):
+        _fields_ = [("nodes_in", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32), ("levels", ctypes.c_uint32),
+                    ("points", ctypes.c_uint64), ("visited", ctypes.c_uint64), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float),
+                    ("total_ms", ctypes.c_float), ("pad_", ctypes.c_uint32)]
+
+
+    assert (ctypes.sizeof(Clearance), ctypes.sizeof(OffsetOptions), ctypes.sizeof(OffsetStats)) == (32, 20, 48)
 
 
     class Probe(ctypes.Structure):
@@ -388,6 +414,9 @@ _SIG = {
     "sdfhip_scene_prune": (_c.c_int, [_vp, _c.POINTER(PruneOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PruneStats)]),
     "sdfhip_scene_combine": (_c.c_int, [_vp, _vp, _c.c_int32, _c.POINTER(CombineOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(CombineStats)]),
     "sdfhip_scene_place": (_c.c_int, [_vp, _c.POINTER(Placement), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PlaceStats)]),
+    "sdfhip_scene_distance": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_int32, _vp]),
+    "sdfhip_scene_distance_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_int32, _vp, _vp]),
+    "sdfhip_scene_offset": (_c.c_int, [_vp, _c.POINTER(OffsetOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(OffsetStats)]),
     "sdfhip_scene_sample": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
     "sdfhip_scene_sample_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),

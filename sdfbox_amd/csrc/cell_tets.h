@@ -1,6 +1,7 @@
-// The cells of a resident scene and their Kuhn tetrahedra (gfx950): what surface extraction (mesh_kernels.h) and the measure
-// (measure_kernels.h) share, so that the two contracts read one definition -- which nodes are cells of a level, which corners are
-// inside, the six tetrahedra and their triangles, the climb for a node's depth.  Non-template device helpers and one constant table;
+// The cells of a resident scene and their Kuhn tetrahedra (gfx950): what surface extraction (mesh_kernels.h), the measure
+// (measure_kernels.h) and the nearest-surface search (distance_kernels.h) share, so that the contracts read one definition -- which
+// nodes are cells of a level, which corners are inside, the six tetrahedra and their triangles, where a cut edge's vertex sits, the
+// climb for a node's depth.  Non-template device helpers and one constant table;
 // no kernel.  The rule is N7's (include/sdfhip.h, sdfhip_scene_mesh).
 #pragma once
 #include "raymarch_device.h"
@@ -60,6 +61,22 @@ __device__ __forceinline__ uint32_t cell_triangles(uint32_t in8)
         n += pc == 2u ? 2u : (pc & 1u);
     }
     return n;
+}
+
+// The position of the vertex on the cut edge from cube corner lo to cube corner hi (the bits of lo are a subset of hi's) of the cell
+// with bytes (v0, v1), integer coordinates (cx, cy, cz) of its depth and edge `scale`: the surface's crossing at byte 63.75 along the
+// edge.  The emitted position of sdfhip_scene_mesh (cut_vertex, mesh_kernels.h) and the triangle corner the nearest-surface search
+// recomputes (distance_kernels.h): one definition, so the two are the same bits.
+__device__ __forceinline__ void cut_position(uint32_t v0, uint32_t v1, float scale, uint32_t cx, uint32_t cy, uint32_t cz, uint32_t lo, uint32_t hi,
+                                             float &px, float &py, float &pz)
+{
+    const unsigned long long bytes = ((unsigned long long)v1 << 32) | v0;
+    const float b_lo = (float)(uint32_t)((bytes >> (8u * lo)) & 0xFFull), b_hi = (float)(uint32_t)((bytes >> (8u * hi)) & 0xFFull);
+    const float t = (63.75f - b_lo) / (b_hi - b_lo);
+    const uint32_t d = lo ^ hi;
+    px = ((float)(cx + (lo & 1u)) + ((d & 1u) ? t : 0.0f)) * scale;
+    py = ((float)(cy + ((lo >> 1) & 1u)) + ((d & 2u) ? t : 0.0f)) * scale;
+    pz = ((float)(cz + ((lo >> 2) & 1u)) + ((d & 4u) ? t : 0.0f)) * scale;
 }
 
 // depth of node i: the links up to the root (mixed nodes of a level >= 0 pass only)

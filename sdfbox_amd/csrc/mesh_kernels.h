@@ -151,16 +151,11 @@ __device__ __forceinline__ void store_triangle(float *__restrict__ verts6, uint3
 }
 
 // The vertex on the cut edge from cube corner lo to cube corner hi (the bits of lo are a subset of hi's) of the cell with integer
-// coordinates (cx, cy, cz) of its depth, edge S: position, then gradient() there times 1 / sqrt(dot(g, g)), as sdfhip_hit.normal
+// coordinates (cx, cy, cz) of its depth, edge S: position (cut_position, cell_tets.h), then gradient() there times 1 / sqrt(dot(g, g)), as sdfhip_hit.normal
 __device__ __forceinline__ void cut_vertex(const Cell &cell, uint32_t cx, uint32_t cy, uint32_t cz, uint32_t lo, uint32_t hi, float *o)
 {
-    const unsigned long long bytes = ((unsigned long long)cell.v1 << 32) | cell.v0;
-    const float b_lo = (float)(uint32_t)((bytes >> (8u * lo)) & 0xFFull), b_hi = (float)(uint32_t)((bytes >> (8u * hi)) & 0xFFull);
-    const float t = (63.75f - b_lo) / (b_hi - b_lo);
-    const uint32_t d = lo ^ hi;
-    const float px = ((float)(cx + (lo & 1u)) + ((d & 1u) ? t : 0.0f)) * cell.scale;
-    const float py = ((float)(cy + ((lo >> 1) & 1u)) + ((d & 2u) ? t : 0.0f)) * cell.scale;
-    const float pz = ((float)(cz + ((lo >> 2) & 1u)) + ((d & 4u) ? t : 0.0f)) * cell.scale;
+    float px, py, pz;
+    cut_position(cell.v0, cell.v1, cell.scale, cx, cy, cz, lo, hi, px, py, pz);
     float gx, gy, gz;
     gradient(cell, px, py, pz, gx, gy, gz);
     const float rg = 1.0f / sqrtf(dot3(gx, gy, gz, gx, gy, gz));

@@ -15,6 +15,7 @@
 #pragma once
 #include "sdf_bytes.h"
 #include "scan_device.h"     // block_exclusive_scan
+#include "tri_dist.h"        // tri_dot, tri_dist2
 
 namespace sdfhip {
 
@@ -30,55 +31,7 @@ struct TriBlock {                         // 32 bytes
     uint32_t cnt, nchild;                 // nchild: 8, or 1 for the root
 };
 
-__device__ __forceinline__ float tri_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
-// D of the rule; r = p - q and the region (0 face, 1 edge ab, 2 edge bc, 3 edge ca, 4 vertex a, 5 b, 6 c: the normal is at floats
-// 9 + 3 * region of the record)
-__device__ __forceinline__ float tri_dist2(const float *T, float px, float py, float pz, float &rx, float &ry, float &rz, int &region)
-{
-    const float ax = T[0], ay = T[1], az = T[2], bx = T[3], by = T[4], bz = T[5], cx = T[6], cy = T[7], cz = T[8];
-    const float abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
-    const float apx = px - ax, apy = py - ay, apz = pz - az;
-    const float d1 = tri_dot(abx, aby, abz, apx, apy, apz), d2 = tri_dot(acx, acy, acz, apx, apy, apz);
-    float qx, qy, qz;
-    if (d1 <= 0.0f && d2 <= 0.0f) { qx = ax; qy = ay; qz = az; region = 4; }
-    else {
-        const float bpx = px - bx, bpy = py - by, bpz = pz - bz;
-        const float d3 = tri_dot(abx, aby, abz, bpx, bpy, bpz), d4 = tri_dot(acx, acy, acz, bpx, bpy, bpz);
-        if (d3 >= 0.0f && d4 <= d3) { qx = bx; qy = by; qz = bz; region = 5; }
-        else {
-            const float vc = d1 * d4 - d3 * d2;
-            if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
-                const float v = d1 / (d1 - d3);
-                qx = ax + abx * v; qy = ay + aby * v; qz = az + abz * v; region = 1;
-            } else {
-                const float cpx = px - cx, cpy = py - cy, cpz = pz - cz;
-                const float d5 = tri_dot(abx, aby, abz, cpx, cpy, cpz), d6 = tri_dot(acx, acy, acz, cpx, cpy, cpz);
-                if (d6 >= 0.0f && d5 <= d6) { qx = cx; qy = cy; qz = cz; region = 6; }
-                else {
-                    const float vb = d5 * d2 - d1 * d6;
-                    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
-                        const float w = d2 / (d2 - d6);
-                        qx = ax + acx * w; qy = ay + acy * w; qz = az + acz * w; region = 3;
-                    } else {
-                        const float va = d3 * d6 - d5 * d4;
-                        const float e0 = d4 - d3, e1 = d5 - d6;
-                        if (va <= 0.0f && e0 >= 0.0f && e1 >= 0.0f) {
-                            const float w = e0 / (e0 + e1);
-                            qx = bx + (cx - bx) * w; qy = by + (cy - by) * w; qz = bz + (cz - bz) * w; region = 2;
-                        } else {
-                            const float den = 1.0f / ((va + vb) + vc);
-                            const float v = vb * den, w = vc * den;
-                            qx = (ax + abx * v) + acx * w; qy = (ay + aby * v) + acy * w; qz = (az + abz * v) + acz * w; region = 0;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    rx = px - qx; ry = py - qy; rz = pz - qz;
-    return tri_dot(rx, ry, rz, rx, ry, rz);
-}
+// tri_dot and tri_dist2 (D of the rule, r = p - q and the region): tri_dist.h, shared with the nearest-surface search
 
 // point `p` of a block: 0..26 lattice corner i + 3j + 9k, 27..34 the centre of child p - 27
 __device__ __forceinline__ void tri_point(const TriBlock &B, int p, float S, float &px, float &py, float &pz)

@@ -235,6 +235,51 @@ class Scene:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
 
+    # -- exact distance (sdfhip_scene_distance / _offset): clearance, offset and shell ------------------------------------------------
+    def Distance(self, points, level=-1):
+        """The exact signed distance from points (n, 3) float32 to this scene's surface -- the triangles Mesh(level) emits -- at any
+        range, where Sample's distance saturates one leaf edge away: a structured array of n records (fields of sdfhip_clearance:
+        distance, node, nearest, status, visited).  A non-finite point gets QUERY_INVALID and zeros; an empty surface gives +-inf."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(p), dtype=np.dtype(_lib.Clearance))
+        check(lib.sdfhip_scene_distance(self._h, p.ctypes.data, len(p), int(level), out.ctypes.data))
+        return out
+
+    def DistanceDevice(self, xyz_ptr, n, out_ptr, level=-1, stream=None):
+        """Distance for n points (n x 3 floats) in device memory at `xyz_ptr` into n sdfhip_clearance records at `out_ptr`,
+        asynchronously on `stream` (a raw hipStream_t value or None), as SampleDevice."""
+        check(lib.sdfhip_scene_distance_device(self._h, ctypes.c_void_p(int(xyz_ptr)), int(n), int(level), ctypes.c_void_p(int(out_ptr)),
+                                               ctypes.c_void_p(int(stream)) if stream else None))
+
+    def _offset(self, mode, amount, depth, level, want_octdata, want_stats):
+        from .octdata import OctData
+        opt = _lib.OffsetOptions(mode, amount, depth, level)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = self.device
+        raw = _lib.COctData()
+        st = _lib.OffsetStats()
+        check(lib.sdfhip_scene_offset(self._h, ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def Offset(self, delta, depth=None, level=-1, want_octdata=False, want_stats=False):
+        """Offset (sdfhip_scene_offset, OFFSET_GROW): this scene's solid grown by `delta` (shrunk when it is negative) -- the tree of
+        Distance(p) - delta -- as a NEW Scene in breadth-first order on the same device; this one is left as it was.  depth: None =
+        this tree's depth, else 0..12; level: the source surface's level, as Mesh.  Nothing is pruned (chain Prune).  want_octdata:
+        also the result's host arrays; want_stats: an OffsetStats."""
+        return self._offset(_lib.OFFSET_GROW, delta, depth, level, want_octdata, want_stats)
+
+    def Shell(self, thickness, depth=None, level=-1, want_octdata=False, want_stats=False):
+        """Shell (sdfhip_scene_offset, OFFSET_SHELL): the wall of `thickness` > 0 centred on this scene's surface -- the tree of
+        abs(Distance(p)) - thickness / 2 -- as a NEW Scene; the arguments are Offset's."""
+        return self._offset(_lib.OFFSET_SHELL, thickness, depth, level, want_octdata, want_stats)
+
     # -- point and ray queries (sdfhip_scene_sample / _raycast / _pick): answers without a frame ---------------------------------
     def Sample(self, points):
         """Distance, cell and gradient at points (n, 3) float32, with the shader's own arithmetic: a structured array of n records
