@@ -258,6 +258,34 @@ public:
     {
         OffsetAs(SDFHIP_OFFSET_SHELL, thickness, depth, level, stats, host_out, "Shell: no model loaded");
     }
+    // Smooth blends and morphs (sdfhip_scene_blend; nothing in the reference corresponds).  Blend: the loaded model becomes its smooth
+    // union (SDFHIP_BLEND_UNION), intersection (_INTERSECT) or difference (_SUBTRACT: this model without the other) with the model
+    // `other` has loaded on the same device (it may be this Program), on the two exact distances: a fillet of `radius` >= 0 where the
+    // surfaces meet, the hard operation at 0.  Morph: the in-between a + (b - a) * t, 0 <= t <= 1; refused when either surface is
+    // empty.  Each a new tree of at most `depth` levels (-1 = the deeper of the two models' depths, else 0..12), which replaces the
+    // loaded model as Combine's result does; `other` keeps its own.  level, other_level: each surface's level.  Nothing is pruned
+    // (chain Prune).  host_out (may be null): the result's host arrays
+    void Blend(const Program &other, int op, float radius, int depth = -1, int level = -1, int other_level = -1, sdfhip_blend_stats *stats = nullptr,
+               sdfhip_octdata *host_out = nullptr)
+    {
+        if (!scene || !other.scene) throw Error(SDFHIP_ERR_ARG, "Blend: no model loaded");
+        sdfhip_blend_options opt = {};
+        opt.size = (uint32_t)sizeof(sdfhip_blend_options);
+        opt.op = op;
+        opt.amount = radius;
+        opt.depth = depth;
+        opt.level_a = level;
+        opt.level_b = other_level;
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_blend(scene, other.scene, &opt, &fresh, host_out, stats));
+        sdfhip_scene_free(scene);
+        scene = fresh;
+    }
+    void Morph(const Program &other, float t, int depth = -1, int level = -1, int other_level = -1, sdfhip_blend_stats *stats = nullptr,
+               sdfhip_octdata *host_out = nullptr)
+    {
+        Blend(other, SDFHIP_BLEND_MORPH, t, depth, level, other_level, stats, host_out);
+    }
     // Point and ray queries (sdfhip_scene_sample / _raycast / _pick; nothing in the reference corresponds): what the loaded model
     // answers without drawing a frame, with the shader's own arithmetic.  Sample: distance, cell and gradient at points (xyz: 3 floats
     // per point); Raycast: the primary march of Compute.hlsl:194-203 for arbitrary rays; Pick: that march for pixels {x, y} of the

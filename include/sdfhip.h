@@ -888,6 +888,65 @@ SDFHIP_API int sdfhip_scene_distance_device(sdfhip_scene *scene, const float *d_
 SDFHIP_API int sdfhip_scene_offset(sdfhip_scene *scene, const sdfhip_offset_options *opt, sdfhip_scene **out, sdfhip_octdata *host_out,
                                    sdfhip_offset_stats *stats);
 
+/* ---- smooth blends and morphs of two resident scenes on the exact distance ----------------------------
+ * Replaces: nothing in the reference's code -- a tree there is immutable once built.  sdfhip_scene_combine takes min / max of stored
+ * bytes, and a stored byte is a distance only in a thin band round the surface, so nothing could be blended there.  On the exact
+ * distance above a fillet between two parts and an in-between of two shapes are one value each.  sdfhip_scene_blend builds the tree
+ * of that value as a NEW handle.  The rule, pinned (fp32, each operation rounded on its own in the order written; S = 2^-d):
+ *   a, b             a = dist_A(p), b = dist_B(p): dist(p) of sdfhip_scene_offset, word for word, on each operand -- the surface of
+ *                    level_a / level_b, the sign from the operand's own sampled distance at the clamped point.  An empty surface
+ *                    gives +inf or -inf
+ *   smin(a, b, k)    h = k > 0.0f ? fmaxf(k - fabsf(a - b), 0.0f) / k : 0.0f;  smin = fminf(a, b) - ((h * h) * k) * 0.25f.
+ *                    fmaxf / fminf return the operand that is not a NaN: inf - inf gives h = 0, and every case with an empty operand
+ *                    is defined
+ *   value(p)         SDFHIP_BLEND_UNION: smin(a, b, k); SDFHIP_BLEND_INTERSECT: -smin(-a, -b, k); SDFHIP_BLEND_SUBTRACT:
+ *                    -smin(-a, b, k) (A without B); SDFHIP_BLEND_MORPH: a + (b - a) * t
+ *   amount           k, the blend radius in units of the cube (finite, >= 0), for the three smooth ops; t (finite, 0 <= t <= 1) for
+ *                    the morph
+ *   tree             sdfhip_scene_place's / sdfhip_scene_offset's, word for word, with this value: byte = FromFloat(value, S); a
+ *                    node splits iff fabsf(value(centre)) < 2 * S && d < depth; breadth-first node order; every point evaluated as if
+ *                    alone.  Nothing is pruned: chain sdfhip_scene_prune
+ * What follows from the rule: k = 0 gives the hard operation on exact distances (h = 0: fminf(a, b) and its mirror images), which is
+ * not sdfhip_scene_combine's bytes.  t = 0 gives a exactly ((b - a) * 0 is a zero), so Morph(A, B, 0) is Offset(A, 0) byte for byte
+ * when B's surface is not empty.  UNION with a B whose root is a leaf of bytes 255 (all outside, no surface: b = +inf, h = 0) is
+ * Offset(A, 0) byte for byte, for any k.  smin >= fminf(a, b) - k / 4: two solids a gap g apart grow a bridge iff k > 2 g -- at the
+ * midpoint a = b = g / 2 and the value is g / 2 - k / 4.
+ * A morph with an empty surface: inf * 0 and inf - inf have no meaning worth pinning, so the call refuses with SDFHIP_ERR_ARG when
+ * either operand's surface (at its level) is empty.
+ * Both inputs are untouched (frames in flight on them included), a == b is allowed, the operands are on the same device, and each
+ * handle's lock is held only while its description is read.  opt: the caller sets size = sizeof(sdfhip_blend_options); the struct
+ * grows like sdfhip_prune_options.  depth: -1 = the deeper of the two operands' depths, else 0..12; level_a, level_b: -1 or 0..12,
+ * each operand surface's level.  out, host_out: either may be NULL, not both.  stats (may be NULL): points counts the evaluated
+ * points (9 for the root, 35 for every block of eight siblings), visited_a / visited_b the records the searches of A's and of B's
+ * surface loaded: the same on every call.
+ * SDFHIP_ERR_ARG: a null scene or options, both outputs NULL, a size the growth rule refuses, an unknown op, a non-finite amount,
+ * k < 0, t outside [0, 1], depth or a level outside -1..12, operands on different devices -- each before any device call -- and a
+ * result of more than 2^31 - 1 nodes, and the morph's refusal above; SDFHIP_ERR_BAD_TREE: an operand sdfhip_scene_mesh refuses;
+ * SDFHIP_ERR_NOMEM: out of device memory (the inputs stay valid, nothing leaks).
+ * The kernel (csrc/blend_kernels.h) is the offset's level pass with two searches per point, one after the other: every point of the
+ * result searches both surfaces, the far one included, which is where the time goes (DESIGN.md N14 has the measurements). */
+enum { SDFHIP_BLEND_UNION = 0, SDFHIP_BLEND_INTERSECT = 1, SDFHIP_BLEND_SUBTRACT = 2, SDFHIP_BLEND_MORPH = 3 };
+typedef struct sdfhip_blend_options {
+    uint32_t size;            /* sizeof(sdfhip_blend_options) of the caller's header */
+    int32_t op;               /* SDFHIP_BLEND_* */
+    float amount;             /* UNION, INTERSECT, SUBTRACT: the blend radius k >= 0; MORPH: t in [0, 1] */
+    int32_t depth;            /* -1 = the deeper of the operands' depths; else 0..12 */
+    int32_t level_a;          /* A's surface level: -1 = full detail; else 0..12 */
+    int32_t level_b;          /* B's */
+} sdfhip_blend_options;       /* 24 bytes */
+typedef struct sdfhip_blend_stats {
+    uint32_t nodes_a, nodes_b, nodes_out, depth_out, levels, pad0_;
+    uint64_t points;         /* points evaluated */
+    uint64_t visited_a;      /* records the searches of A's surface loaded */
+    uint64_t visited_b;      /* ... of B's */
+    float kernel_ms;         /* HIP events around the call's kernels (the per-level host synchronisations included) */
+    float scene_ms;          /* building the new handle, host clock */
+    float total_ms;          /* host clock, the whole call */
+    uint32_t pad_;
+} sdfhip_blend_stats;        /* 64 bytes */
+SDFHIP_API int sdfhip_scene_blend(sdfhip_scene *a, sdfhip_scene *b, const sdfhip_blend_options *opt, sdfhip_scene **out,
+                                  sdfhip_octdata *host_out, sdfhip_blend_stats *stats);
+
 /* ---- triangle mesh -> ASDF: exact signed distance on the GPU ------------------------------------------
  * Replaces: nothing in the live reference -- SdfGen builds from the nearest POINT of a cloud (dllmain.cpp:117-161), which
  * sdfhip_sdfgen restates.  It is the intent of the reference's abandoned per-triangle GPU generator (SdfBox/GpuGenerator.cs +

@@ -46,13 +46,14 @@ EDIT_CARVE, EDIT_ADD = 0, 1          # sdfhip_scene_edit: subtract / union
 BRUSH_SPHERE, BRUSH_BOX = 0, 1
 COMBINE_UNION, COMBINE_INTERSECT, COMBINE_SUBTRACT = 0, 1, 2      # sdfhip_scene_combine: A or B, A and B, A without B
 OFFSET_GROW, OFFSET_SHELL = 0, 1     # sdfhip_scene_offset: dist - amount / fabsf(dist) - amount / 2
+BLEND_UNION, BLEND_INTERSECT, BLEND_SUBTRACT, BLEND_MORPH = 0, 1, 2, 3      # sdfhip_scene_blend: smooth A or B, A and B, A without B; the in-between
 QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdfhip_probe.status / sdfhip_hit.status
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Clearance, OffsetOptions, OffsetStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -243,6 +244,27 @@ else:
     assert (ctypes.sizeof(Clearance), ctypes.sizeof(OffsetOptions), ctypes.sizeof(OffsetStats)) == (32, 20, 48)
 
 
+    class BlendOptions(ctypes.Structure):
+        """sdfhip_blend_options: op BLEND_UNION / _INTERSECT / _SUBTRACT (amount = the blend radius k >= 0) or BLEND_MORPH (amount = t in
+        [0, 1]); depth None = the deeper of the operands' depths, else 0..12; level_a, level_b: each operand surface's level, -1 = full
+        detail."""
+        _fields_ = [("size", ctypes.c_uint32), ("op", ctypes.c_int32), ("amount", ctypes.c_float), ("depth", ctypes.c_int32),
+                    ("level_a", ctypes.c_int32), ("level_b", ctypes.c_int32)]
+
+        def __init__(self, op=0, amount=0.0, depth=None, level_a=-1, level_b=-1):
+            super().__init__(ctypes.sizeof(type(self)), int(op), float(amount), -1 if depth is None else int(depth), int(level_a), int(level_b))
+
+
+    class BlendStats(ctypes.Structure):
+        _fields_ = [("nodes_a", ctypes.c_uint32), ("nodes_b", ctypes.c_uint32), ("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32),
+                    ("levels", ctypes.c_uint32), ("pad0_", ctypes.c_uint32), ("points", ctypes.c_uint64), ("visited_a", ctypes.c_uint64),
+                    ("visited_b", ctypes.c_uint64), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
+                    ("pad_", ctypes.c_uint32)]
+
+
+    assert (ctypes.sizeof(BlendOptions), ctypes.sizeof(BlendStats)) == (24, 64)
+
+
     class Probe(ctypes.Structure):
         """sdfhip_probe: the answer for one point of sdfhip_scene_sample."""
         _fields_ = [("distance", ctypes.c_float), ("node", ctypes.c_uint32), ("scale", ctypes.c_float), ("status", ctypes.c_uint32),
@@ -417,6 +439,7 @@ _SIG = {
     "sdfhip_scene_distance": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_int32, _vp]),
     "sdfhip_scene_distance_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_int32, _vp, _vp]),
     "sdfhip_scene_offset": (_c.c_int, [_vp, _c.POINTER(OffsetOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(OffsetStats)]),
+    "sdfhip_scene_blend": (_c.c_int, [_vp, _vp, _c.POINTER(BlendOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(BlendStats)]),
     "sdfhip_scene_sample": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
     "sdfhip_scene_sample_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),

@@ -10,12 +10,11 @@
 //   value     GROW dist - delta; SHELL fabsf(dist) - thickness * 0.5f      tree    sdfhip_scene_place's construct rule and node order
 //
 // Per call: the "surface below" bitmap (k_dist_mark: 4 bytes per 32 nodes, zeroed and rebuilt every time -- nothing is kept on the
-// handle), then either k_dist_query, or the placement's level loop (build_levels below) with k_offset_level as its first pass, the
+// handle), then either k_dist_query, or the placement's level loop (level_build.h's build_levels) with k_offset_level as its first pass, the
 // shared bitmap scan and k_offset_emit.  The _device form launches on the caller's stream and returns; its bitmap is one block per device kept here, and a
 // call waits for the query that last read it -- through the library's own event, never the caller's stream -- before it writes it
 // again (as mesh.hip's chunk totals).  The host form and the offset run on a stream of their own with memory of their own.
-#include "distance_kernels.h"
-#include "host_support.h"
+#include "level_build.h"      // distance_kernels.h, host_support.h; Source, launch_mark, build_levels
 #include "abi_guard.h"
 
 #include <algorithm>
@@ -25,6 +24,7 @@
 #include <type_traits>
 
 using namespace sdfhip;
+using namespace sdfhip::levels;
 
 static_assert(sizeof(sdfhip_clearance) == 32 && sizeof(sdfhip_offset_options) == 20 && sizeof(sdfhip_offset_stats) == 48,
               "the distance records of include/sdfhip.h");
@@ -32,60 +32,6 @@ static_assert(SDFHIP_OFFSET_GROW == OFFSET_GROW && SDFHIP_OFFSET_SHELL == OFFSET
               SDFHIP_QUERY_INVALID == QUERY_INVALID, "distance_kernels.h restates the header's codes");
 
 namespace {
-
-constexpr int MAX_DEVICES = 64;
-constexpr uint32_t DIST_MAX_WORKGROUPS = 2048;      // every pass strides with at most this many workgroups of four waves: 8 waves on each of the 1024 SIMDs
-
-// The sign's look-up takes the march's cursor, as the placement's value does: the grid wherever the handle has a full-depth one,
-// else the walk along the links.  Both give the same bytes.
-enum Form { FORM_GENERIC = 0, FORM_GRID = 1, FORM_SPLIT = 2 };
-Form form_of(const sdfhip_scene *s)
-{
-    if (!scene_has_full_depth_grid(s)) return FORM_GENERIC;
-    return s->fine_bits ? FORM_SPLIT : FORM_GRID;
-}
-QueryScene scene_of(const sdfhip_scene *s)
-{
-    return QueryScene{s->nodes, s->n, s->d_top, s->d_fine, s->top_level, s->fine_bits};
-}
-
-// what a call reads of the handle, under its lock
-struct Source {
-    QueryScene Q;
-    Form form;
-    uint32_t depth;
-    int device, stack_ok;
-};
-Source read_source(sdfhip_scene *s)
-{
-    std::lock_guard<std::mutex> lk(s->lock);
-    return Source{scene_of(s), form_of(s), s->depth, s->device, s->stack_ok};
-}
-// sdfhip_scene_mesh's refusal: the surface is its triangles
-int check_source(const char *what, const Source &src)
-{
-    if (!src.stack_ok || src.depth > (uint32_t)MESH_MAX_DEPTH)
-        return fail(SDFHIP_ERR_BAD_TREE, "%s: the tree is not consistent (or deeper than %d levels): it has no mesh, so no surface to measure from", what,
-                    MESH_MAX_DEPTH);
-    if (src.device < 0 || src.device >= MAX_DEVICES) return fail(SDFHIP_ERR_ARG, "%s: device %d", what, src.device);
-    return SDFHIP_OK;
-}
-int check_level(const char *what, int32_t level)
-{
-    if (level < -1 || level > MESH_MAX_DEPTH) return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, level, MESH_MAX_DEPTH);
-    return SDFHIP_OK;
-}
-
-size_t bitmap_words(uint32_t n) { return ((size_t)n + 31) / 32 + 1; }     // (+ 1: sibling_bits reads one word past a block's first)
-
-// (a) on `st`: the bitmap zeroed and marked
-int launch_mark(const Source &src, int32_t level, uint32_t *below, hipStream_t st)
-{
-    HIP_TRY(hipMemsetAsync(below, 0, bitmap_words(src.Q.n_nodes) * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_dist_mark, grid_stride_blocks(src.Q.n_nodes, DIST_MAX_WORKGROUPS), dim3(DIST_THREADS), 0, st, src.Q.nodes, src.Q.n_nodes, (int)level, below);
-    HIP_TRY(hipGetLastError());
-    return SDFHIP_OK;
-}
 
 int launch_query(const Source &src, const DistScene &D, const float *d_xyz, uint32_t n, sdfhip_clearance *d_out, hipStream_t st)
 {
@@ -122,97 +68,6 @@ struct Temp {
     bool pending = false;
 };
 Temp g_temp[MAX_DEVICES];
-
-struct LevelBuild {
-    int2 *dS = nullptr;            // the result's links and bytes, in `bufs`
-    uint2 *dV = nullptr;
-    uint32_t n_out = 1, depth_out = 0;
-    uint64_t points = 0;           // 9 for the root and 35 for every block of eight siblings
-};
-
-// The level loop, as place.hip runs it for the placement (a sibling: that translation unit stays as it was).
-// what: the entry point's name for the messages.  nodes_in: the source's size, which the arrays start from.  launch_level(blocks,
-// nblocks, nchild, S, may_split, V, split): launches the level's first pass on `st`.  Throws NoMem (DeviceBuffers).  The last
-// level may still be in flight on `st` when it returns: the caller waits.
-template <class LaunchLevel>
-int build_levels(const char *what, DeviceBuffers &bufs, hipStream_t st, uint32_t nodes_in, int depth, LaunchLevel launch_level, LevelBuild &R)
-{
-    // The result's arrays start with room for a tree of the source's size and double when a level does not fit: the levels
-    // already written are copied over.  The per-level buffers are sized for what the arrays can hold -- a level is part of the
-    // result -- and follow when those grow.  Every buffer is replaced only while the stream is idle.
-    size_t cap = std::min<size_t>(std::max<size_t>((size_t)nodes_in + nodes_in / 2, 4096), 0x7FFFFFFFull);
-    R.dS = bufs.get<int2>(cap);
-    R.dV = bufs.get<uint2>(cap);
-    bool idle = true;
-    const auto room = [&](auto *&p, size_t &have, size_t need) -> int {       // contents not kept
-        if (need <= have) return SDFHIP_OK;
-        if (!idle) { HIP_TRY(hipStreamSynchronize(st)); idle = true; }
-        if (p) bufs.drop(p);
-        p = nullptr; have = 0;
-        p = bufs.get<typename std::remove_reference<decltype(*p)>::type>(need);
-        have = need;
-        return SDFHIP_OK;
-    };
-    const auto grown = [&](auto *&p, size_t new_cap, size_t keep) -> int {    // the stream is idle
-        auto *q = bufs.get<typename std::remove_reference<decltype(*p)>::type>(new_cap);
-        HIP_TRY(hipMemcpyAsync(q, p, keep * sizeof *p, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        bufs.drop(p);
-        p = q;
-        return SDFHIP_OK;
-    };
-    const auto words_of = [](size_t nodes) { return (nodes + 31) / 32; };
-    OffsetBlock *cur = nullptr, *next = nullptr;
-    uint32_t *split = nullptr, *pre = nullptr, *chunk = nullptr;
-    size_t cur_cap = 0, next_cap = 0, split_cap = 0, pre_cap = 0, chunk_cap = 0;
-    if (const int rc = room(cur, cur_cap, cap / 8 + 1)) return rc;
-    HIP_TRY(hipMemsetAsync(cur, 0, sizeof(OffsetBlock), st));                 // the root's block: the cell at the origin
-    HIP_TRY(hipMemsetAsync(R.dS, 0xFF, sizeof(int2), st));                   // the root: {-1, -1}
-
-    uint32_t first = 0, n = 1, nblocks = 1, nchild = 1;
-    for (int d = 0;; d++) {
-        R.depth_out = (uint32_t)d;
-        const float S = ldexpf(1.0f, -d);
-        const int may_split = d < depth ? 1 : 0;
-        const uint32_t m = (n + 31) / 32, nchunk = (m + 1023) / 1024;
-        if (const int rc = room(split, split_cap, words_of(cap))) return rc;
-        if (const int rc = room(pre, pre_cap, words_of(cap))) return rc;
-        if (const int rc = room(chunk, chunk_cap, (words_of(cap) + 1023) / 1024 + 1)) return rc;        // (+ 1: the level's splits)
-        idle = false;
-        launch_level(cur, nblocks, nchild, S, may_split, R.dV + first, reinterpret_cast<uint8_t *>(split));
-        HIP_TRY(hipGetLastError());
-        R.points += nchild == 1 ? 9u : (uint64_t)OFFSET_POINTS * nblocks;
-        if (!may_split) break;
-        hipLaunchKernelGGL(k_rank_scan_words<OffsetSplitWords>, dim3(nchunk), dim3(256), 0, st, OffsetSplitWords{ split, n }, m, pre, chunk);
-        hipLaunchKernelGGL(k_rank_scan_chunks<true>, dim3(1), dim3(1024), 0, st, chunk, nchunk);
-        HIP_TRY(hipGetLastError());
-        uint32_t n_split = 0;
-        HIP_TRY(hipMemcpyAsync(&n_split, chunk + nchunk, sizeof n_split, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        idle = true;
-        if (!n_split) break;
-        if (n_split > n) return fail(SDFHIP_ERR_DEVICE, "%s: %u splits among %u nodes", what, n_split, n);
-        const uint64_t total = (uint64_t)R.n_out + 8ull * n_split;
-        if (total > 0x7FFFFFFFull) return fail(SDFHIP_ERR_ARG, "%s: the result would have more than 2^31 - 1 nodes", what);
-        if (total > cap) {
-            const size_t new_cap = (size_t)std::min<uint64_t>(std::max<uint64_t>(total, 2ull * cap), 0x7FFFFFFFull);
-            if (const int rc = grown(R.dS, new_cap, R.n_out)) return rc;
-            if (const int rc = grown(R.dV, new_cap, R.n_out)) return rc;
-            cap = new_cap;
-        }
-        if (const int rc = room(next, next_cap, cap / 8 + 1)) return rc;
-        idle = false;
-        hipLaunchKernelGGL(k_offset_emit, grid_stride_blocks(8ull * n, DIST_MAX_WORKGROUPS), dim3(256), 0, st, cur, n, nchild, first, split, pre,
-                           chunk, R.dS, (uint32_t)cap, next, n_split);
-        HIP_TRY(hipGetLastError());
-        std::swap(cur, next);
-        std::swap(cur_cap, next_cap);
-        first += n;
-        n = 8u * n_split; nblocks = n_split; nchild = 8;
-        R.n_out = (uint32_t)total;
-    }
-    return SDFHIP_OK;
-}
 
 // what the header refuses of the options, before any device call
 int check_offset_options(const sdfhip_offset_options *opt)

@@ -1,6 +1,7 @@
 // The exact distance from a point to the surface a resident scene describes (gfx950): the nearest-surface search, the clearance
-// query built on it, and the level passes of offset and shell.  k_dist_mark and k_offset_emit are not templates: included by
-// distance.hip ONLY.  Host side, C ABI: distance.hip.
+// query built on it, and the level passes of offset and shell.  Included by distance.hip and, for the search, the level pass's body
+// and the two kernels the level loop launches (level_build.h), by blend.hip: k_dist_mark and k_offset_emit, which are not templates,
+// are `static` -- each of the two translation units has its own.  Host side, C ABI: distance.hip.
 //
 // Replaces: nothing in the reference's code -- its field is only ever read as stored, a distance in a thin band round the surface.
 //
@@ -16,7 +17,8 @@
 //   nearest_search  (b) one lane per point, depth first from the root, the children of a node nearest first; a child is skipped when
 //                   its bit is clear or its box cannot hold anything nearer than the best so far (box_gap2 and SEARCH_KEEP below: the
 //                   margin and its derivation); at a cut cell the lane recomputes the cell's triangles and folds tri_dist2 into the best
-//   k_offset_level  (c) place_kernels.h's k_place_level with value(p) = dist(p) - delta, or fabsf(dist(p)) - thickness / 2, and
+//   k_offset_level  (c) place_kernels.h's k_place_level with value(p) = dist(p) - delta, or fabsf(dist(p)) - thickness / 2 (its body
+//                   is offset_level_body, a template on the value, which blend_kernels.h's k_blend_level instantiates too), and
 //   k_offset_emit   its k_place_emit: siblings, not shared definitions -- place_kernels.h's emit is not a template and belongs to
 //                   place.hip alone, and the placement's translation unit stays exactly as it was
 //   k_dist_query    (d) n points in, n sdfhip_clearance records out, a grid-stride loop over the same search
@@ -53,7 +55,7 @@ struct DistScene {
 };
 
 // (a).  `below` was zeroed.  The climb is bounded as node_depth's is: the host side refuses trees that are not consistent.
-__global__ __launch_bounds__(DIST_THREADS) void k_dist_mark(const NodeRec *__restrict__ nodes, uint32_t n, int level, uint32_t *__restrict__ below)
+static __global__ __launch_bounds__(DIST_THREADS) void k_dist_mark(const NodeRec *__restrict__ nodes, uint32_t n, int level, uint32_t *__restrict__ below)
 {
     for (uint64_t j = (uint64_t)blockIdx.x * DIST_THREADS + threadIdx.x; j < n; j += (uint64_t)gridDim.x * DIST_THREADS) {
         const NodeRec r = nodes[j];
@@ -253,15 +255,15 @@ __device__ __forceinline__ float dist_at(const QueryScene &Q, const DistScene &D
     return sign * sqrtf(best.d2);
 }
 
-// (c) k_place_level (place_kernels.h) with the offset's value in place of place_value: the same blocks, lattice, shuffles, ballot
-// and stores.  mode: OFFSET_GROW value = dist - amount; OFFSET_SHELL value = fabsf(dist) - amount, amount = thickness * 0.5f (the
-// host's one multiplication).  visited: the records the level's searches loaded, added up per block in 64 bits.
-template <class CursorT>
-__global__ __launch_bounds__(OFFSET_THREADS) void k_offset_level(QueryScene Q, DistScene D, int mode, float amount, const OffsetBlock *__restrict__ blocks,
-                                                                uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *__restrict__ V,
-                                                                uint8_t *__restrict__ split, unsigned long long *__restrict__ visited)
+// (c) k_place_level (place_kernels.h) with a value functor in place of place_value: the same blocks, lattice, shuffles, ballot and
+// stores.  One body for every level pass built on the exact distance: k_offset_level below and k_blend_level (blend_kernels.h)
+// instantiate it.  Value: SOURCES, the number of surfaces a point is searched against; value_of(px, py, pz, stk, seen) -> value(p),
+// which adds the records each search loaded to seen[0 .. SOURCES - 1]; value_of.visited, SOURCES counters in device memory: the
+// records the level's searches loaded, added up per block in 64 bits.  stack: the workgroup's MESH_MAX_DEPTH * OFFSET_THREADS entries.
+template <class Value>
+__device__ __forceinline__ void offset_level_body(const Value &value_of, const OffsetBlock *__restrict__ blocks, uint32_t nblocks, uint32_t nchild, float S,
+                                                  int may_split, uint2 *__restrict__ V, uint8_t *__restrict__ split, uint2 *stack)
 {
-    __shared__ uint2 stack[MESH_MAX_DEPTH * OFFSET_THREADS];
     constexpr uint32_t WAVES = OFFSET_THREADS / 64;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t li = lane % 3u, lj = lane / 3u % 3u, lk = lane / 9u;           // the lattice corner of a lane < 27
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(OFFSET_THREADS) void k_offset_level(QueryScene Q, D
         // the root's block: the root's own eight corners and its centre
         const bool wanted = nchild == 8u ? lane < (uint32_t)OFFSET_POINTS : lane < 27u ? (li < 2u && lj < 2u && lk < 2u) : lane == 27u;
         float value = 0.0f;
-        uint32_t seen = 0u;
+        uint32_t seen[Value::SOURCES] = {};
         if (wanted) {
             float px, py, pz;
             if (lane < 27u) {
@@ -284,10 +286,7 @@ __global__ __launch_bounds__(OFFSET_THREADS) void k_offset_level(QueryScene Q, D
                 py = (float)(2u * (2u * by + (m >> 1 & 1u)) + 1u) * H;
                 pz = (float)(2u * (2u * bz + (m >> 2)) + 1u) * H;
             }
-            Nearest best;
-            const float dist = dist_at<CursorT, OFFSET_THREADS>(Q, D, px, py, pz, stack + threadIdx.x, best);
-            value = mode == OFFSET_SHELL ? fabsf(dist) - amount : dist - amount;
-            seen = best.visited;
+            value = value_of(px, py, pz, stack + threadIdx.x, seen);
         }
         uint32_t w[2] = { 0u, 0u };
 #pragma unroll
@@ -300,13 +299,43 @@ __global__ __launch_bounds__(OFFSET_THREADS) void k_offset_level(QueryScene Q, D
         const unsigned long long mask = __ballot(splits);
         if (lane < nchild) V[8ull * b + lane] = make_uint2(w[0], w[1]);
         if (lane == 0) split[b] = (uint8_t)mask;
-        // the block's records, added once per block: a search may load up to n_nodes < 2^31 of them, so the wave's sum is made of the
-        // lanes' low and high 16 bits apart (each below 2^22) and put together in 64 bits
-        uint32_t lo = seen & 0xFFFFu, hi = seen >> 16;
+        // the block's records, added once per block and source: a search may load up to n_nodes < 2^31 of them, so the wave's sum is
+        // made of the lanes' low and high 16 bits apart (each below 2^22) and put together in 64 bits
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { lo += (uint32_t)__shfl_xor((int)lo, o); hi += (uint32_t)__shfl_xor((int)hi, o); }
-        if (lane == 0 && (lo | hi)) atomicAdd(visited, ((unsigned long long)hi << 16) + lo);
+        for (int s = 0; s < Value::SOURCES; s++) {
+            uint32_t lo = seen[s] & 0xFFFFu, hi = seen[s] >> 16;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) { lo += (uint32_t)__shfl_xor((int)lo, o); hi += (uint32_t)__shfl_xor((int)hi, o); }
+            if (lane == 0 && (lo | hi)) atomicAdd(value_of.visited + s, ((unsigned long long)hi << 16) + lo);
+        }
     }
+}
+
+// The offset's value.  mode: OFFSET_GROW value = dist - amount; OFFSET_SHELL value = fabsf(dist) - amount, amount = thickness * 0.5f
+// (the host's one multiplication).
+template <class CursorT> struct OffsetValue {
+    static constexpr int SOURCES = 1;
+    QueryScene Q;
+    DistScene D;
+    int mode;
+    float amount;
+    unsigned long long *visited;
+    __device__ __forceinline__ float operator()(float px, float py, float pz, uint2 *stk, uint32_t *seen) const
+    {
+        Nearest best;
+        const float dist = dist_at<CursorT, OFFSET_THREADS>(Q, D, px, py, pz, stk, best);
+        seen[0] = best.visited;
+        return mode == OFFSET_SHELL ? fabsf(dist) - amount : dist - amount;
+    }
+};
+
+template <class CursorT>
+__global__ __launch_bounds__(OFFSET_THREADS) void k_offset_level(QueryScene Q, DistScene D, int mode, float amount, const OffsetBlock *__restrict__ blocks,
+                                                                uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *__restrict__ V,
+                                                                uint8_t *__restrict__ split, unsigned long long *__restrict__ visited)
+{
+    __shared__ uint2 stack[MESH_MAX_DEPTH * OFFSET_THREADS];
+    offset_level_body(OffsetValue<CursorT>{Q, D, mode, amount, visited}, blocks, nblocks, nchild, S, may_split, V, split, stack);
 }
 
 // The split bitmap of a level of n nodes, words 0 .. ceil(n / 32) - 1, to k_rank_scan_words (scan_device.h): the bits from n on
@@ -325,7 +354,7 @@ struct OffsetSplitWords {
 // node's child i.  A splitting node of rank r (the splits before it in the level's order) gets the block first + n + 8 r, appended
 // behind the level: its children link, the eight children's {parent, -1}, and the next level's block r with the node's own
 // coordinates.  cap_out / cap_next: the room in links[] and next[].
-__global__ __launch_bounds__(256) void k_offset_emit(const OffsetBlock *__restrict__ blocks, uint32_t n, uint32_t nchild, uint32_t first,
+static __global__ __launch_bounds__(256) void k_offset_emit(const OffsetBlock *__restrict__ blocks, uint32_t n, uint32_t nchild, uint32_t first,
                                                      const uint32_t *__restrict__ split, const uint32_t *__restrict__ pre,
                                                      const uint32_t *__restrict__ chunk, int2 *__restrict__ links, uint32_t cap_out,
                                                      OffsetBlock *__restrict__ next, uint32_t cap_next)

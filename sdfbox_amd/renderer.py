@@ -280,6 +280,38 @@ class Scene:
         abs(Distance(p)) - thickness / 2 -- as a NEW Scene; the arguments are Offset's."""
         return self._offset(_lib.OFFSET_SHELL, thickness, depth, level, want_octdata, want_stats)
 
+    # -- smooth blends and morphs on the exact distance (sdfhip_scene_blend) ------------------------------------------------------------
+    def Blend(self, other, op, radius, depth=None, level=-1, other_level=-1, want_octdata=False, want_stats=False):
+        """Smooth blend (sdfhip_scene_blend): the smooth union (BLEND_UNION), intersection (BLEND_INTERSECT) or difference
+        (BLEND_SUBTRACT: this scene without `other`) of this scene and `other`, a Scene on the same device (it may be this one), on
+        their exact distances a = Distance_A(p), b = Distance_B(p): the tree of smin(a, b, radius) and its mirror images, smin = min(a,
+        b) - h * h * radius / 4 with h = max(radius - |a - b|, 0) / radius -- a fillet of radius `radius` >= 0 where the two surfaces
+        meet, the hard operation at 0 -- as a NEW Scene in breadth-first order; both inputs are left as they were.  BLEND_MORPH takes
+        `radius` as t (Morph).  depth: None = the deeper of the two trees' depths, else 0..12; level, other_level: each surface's
+        level, as Mesh.  Nothing is pruned (chain Prune).  want_octdata: also the result's host arrays; want_stats: a BlendStats."""
+        from .octdata import OctData
+        opt = _lib.BlendOptions(op, radius, depth, level, other_level)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = self.device
+        raw = _lib.COctData()
+        st = _lib.BlendStats()
+        check(lib.sdfhip_scene_blend(self._h, other._h, ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None,
+                                     ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def Morph(self, other, t, depth=None, level=-1, other_level=-1, want_octdata=False, want_stats=False):
+        """Morph (sdfhip_scene_blend, BLEND_MORPH): the in-between of this scene and `other` -- the tree of a + (b - a) * t, 0 <= t <= 1:
+        this scene's exact field at 0, the other's at 1 -- as a NEW Scene; the other arguments are Blend's.  Refused (ERR_ARG) when
+        either surface is empty."""
+        return self.Blend(other, _lib.BLEND_MORPH, t, depth, level, other_level, want_octdata, want_stats)
+
     # -- point and ray queries (sdfhip_scene_sample / _raycast / _pick): answers without a frame ---------------------------------
     def Sample(self, points):
         """Distance, cell and gradient at points (n, 3) float32, with the shader's own arithmetic: a structured array of n records
