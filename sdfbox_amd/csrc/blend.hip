@@ -10,10 +10,10 @@
 //   tree      sdfhip_scene_offset's construct rule and node order, with this value
 //
 // Per call: the "surface below" bitmap of each operand (k_dist_mark; one when a == b and the levels agree), for a morph one 4-byte
-// read per operand of the root's bit (an empty surface is refused), then the offset's level loop (level_build.h's build_levels) with
+// read per operand of the root's bit (an empty surface is refused), then the shared level loop (level_build.h's build_levels) with
 // k_blend_level as its first pass.  The call runs on a stream of its own with memory of its own; nothing is kept on the handles.
 #include "blend_kernels.h"
-#include "level_build.h"      // host_support.h; Source, launch_mark, build_levels
+#include "distance_host.h"    // check_source, launch_mark; level_build.h: Source, build_levels
 #include "abi_guard.h"
 
 #include <algorithm>
@@ -98,8 +98,8 @@ try {
                 return fail(SDFHIP_ERR_ARG, "%s: operand %s has an empty surface at its level: there is no distance to morph", what, root_a & 1u ? "b" : "a");
         }
         const DistScene DA{A.Q.nodes, A.Q.n_nodes, below_a, opt->level_a}, DB{B.Q.nodes, B.Q.n_nodes, below_b, opt->level_b};
-        const auto level = [&](const OffsetBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
-            hipLaunchKernelGGL(k_blend_level, grid_stride_blocks(64ull * nblocks, DIST_MAX_WORKGROUPS), dim3(OFFSET_THREADS), 0, st, A.Q, DA, B.Q, DB, op, amount,
+        const auto level = [&](const LevelBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
+            hipLaunchKernelGGL(k_blend_level, grid_stride_blocks(64ull * nblocks, LEVEL_MAX_WORKGROUPS), dim3(LEVEL_THREADS), 0, st, A.Q, DA, B.Q, DB, op, amount,
                                blocks, nblocks, nchild, S, may_split, V, split, d_visited);
         };
         // (the arrays start from the two operands' sizes together)

@@ -9,7 +9,7 @@
 //   smin      h = k > 0 ? fmaxf(k - fabsf(a - b), 0) / k : 0;  smin = fminf(a, b) - ((h * h) * k) * 0.25f
 //             (fmaxf / fminf return the operand that is no NaN: inf - inf gives h = 0)
 //   value     UNION smin(a, b, k); INTERSECT -smin(-a, -b, k); SUBTRACT -smin(-a, b, k); MORPH a + (b - a) * t
-//   tree      the construct rule and node order of the offset: k_blend_level is offset_level_body (distance_kernels.h) on BlendValue
+//   tree      the construct rule and node order of the offset: k_blend_level is level_body (level_kernels.h) on BlendValue
 //
 // k_blend_level.  A lane searches A's surface and then B's, one after the other through the SAME slice of the workgroup's stack
 // ([level][lane], 24 576 bytes per workgroup, as the offset's: the first search has left nothing on it that the second needs), keeps
@@ -17,7 +17,8 @@
 // (CursorG) whatever grids the handles have: both forms give the same bytes, the look-up is one find beside a search of about a
 // hundred records, and a kernel per pair of forms would be nine copies of the heaviest kernel in the library.
 #pragma once
-#include "distance_kernels.h"
+#include "distance_kernels.h"   // nearest_search, inside_at, DistScene
+#include "level_kernels.h"      // LevelBlock, LEVEL_THREADS, level_body
 
 namespace sdfhip {
 
@@ -55,13 +56,13 @@ struct BlendValue {
         float root[2];
         {
             Nearest best;
-            nearest_search<OFFSET_THREADS>(DA, px, py, pz, stk, best);
+            nearest_search<LEVEL_THREADS>(DA, px, py, pz, stk, best);
             root[0] = sqrtf(best.d2);
             seen[0] = best.visited;
         }
         {
             Nearest best;
-            nearest_search<OFFSET_THREADS>(DB, px, py, pz, stk, best);
+            nearest_search<LEVEL_THREADS>(DB, px, py, pz, stk, best);
             root[1] = sqrtf(best.d2);
             seen[1] = best.visited;
         }
@@ -71,13 +72,13 @@ struct BlendValue {
     }
 };
 
-__global__ __launch_bounds__(OFFSET_THREADS) void k_blend_level(QueryScene QA, DistScene DA, QueryScene QB, DistScene DB, int op, float amount,
-                                                               const OffsetBlock *__restrict__ blocks, uint32_t nblocks, uint32_t nchild, float S,
+__global__ __launch_bounds__(LEVEL_THREADS) void k_blend_level(QueryScene QA, DistScene DA, QueryScene QB, DistScene DB, int op, float amount,
+                                                               const LevelBlock *__restrict__ blocks, uint32_t nblocks, uint32_t nchild, float S,
                                                                int may_split, uint2 *__restrict__ V, uint8_t *__restrict__ split,
                                                                unsigned long long *__restrict__ visited)
 {
-    __shared__ uint2 stack[MESH_MAX_DEPTH * OFFSET_THREADS];
-    offset_level_body(BlendValue{QA, DA, QB, DB, op, amount, visited}, blocks, nblocks, nchild, S, may_split, V, split, stack);
+    __shared__ uint2 stack[MESH_MAX_DEPTH * LEVEL_THREADS];
+    level_body(BlendValue{QA, DA, QB, DB, op, amount, visited}, blocks, nblocks, nchild, S, may_split, V, split, stack + threadIdx.x);
 }
 
 }  // namespace sdfhip

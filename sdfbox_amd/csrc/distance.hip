@@ -10,11 +10,11 @@
 //   value     GROW dist - delta; SHELL fabsf(dist) - thickness * 0.5f      tree    sdfhip_scene_place's construct rule and node order
 //
 // Per call: the "surface below" bitmap (k_dist_mark: 4 bytes per 32 nodes, zeroed and rebuilt every time -- nothing is kept on the
-// handle), then either k_dist_query, or the placement's level loop (level_build.h's build_levels) with k_offset_level as its first pass, the
-// shared bitmap scan and k_offset_emit.  The _device form launches on the caller's stream and returns; its bitmap is one block per device kept here, and a
+// handle), then either k_dist_query, or the shared level loop (level_build.h's build_levels) with k_offset_level as its first pass.
+// The _device form launches on the caller's stream and returns; its bitmap is one block per device kept here, and a
 // call waits for the query that last read it -- through the library's own event, never the caller's stream -- before it writes it
 // again (as mesh.hip's chunk totals).  The host form and the offset run on a stream of their own with memory of their own.
-#include "level_build.h"      // distance_kernels.h, host_support.h; Source, launch_mark, build_levels
+#include "distance_host.h"    // distance_kernels.h; check_source, launch_mark; level_build.h: Source, with_cursor, build_levels
 #include "abi_guard.h"
 
 #include <algorithm>
@@ -35,26 +35,20 @@ namespace {
 
 int launch_query(const Source &src, const DistScene &D, const float *d_xyz, uint32_t n, sdfhip_clearance *d_out, hipStream_t st)
 {
-    const dim3 grid = grid_stride_blocks(n, DIST_MAX_WORKGROUPS), wg(DIST_THREADS);
+    const dim3 grid = grid_stride_blocks(n, LEVEL_MAX_WORKGROUPS), wg(DIST_THREADS);
     uint4 *out = reinterpret_cast<uint4 *>(d_out);
-    switch (src.form) {
-    case FORM_GRID: hipLaunchKernelGGL((k_dist_query<CursorFT<false, false>>), grid, wg, 0, st, src.Q, D, d_xyz, n, out); break;
-    case FORM_SPLIT: hipLaunchKernelGGL((k_dist_query<CursorFT<false, true>>), grid, wg, 0, st, src.Q, D, d_xyz, n, out); break;
-    default: hipLaunchKernelGGL((k_dist_query<CursorG>), grid, wg, 0, st, src.Q, D, d_xyz, n, out); break;
-    }
+    with_cursor(src.form, [&](auto c) { hipLaunchKernelGGL((k_dist_query<typename decltype(c)::type>), grid, wg, 0, st, src.Q, D, d_xyz, n, out); });
     HIP_TRY(hipGetLastError());
     return SDFHIP_OK;
 }
 
-void launch_level(const Source &src, const DistScene &D, int mode, float amount, const OffsetBlock *blocks, uint32_t nblocks, uint32_t nchild,
+void launch_level(const Source &src, const DistScene &D, int mode, float amount, const LevelBlock *blocks, uint32_t nblocks, uint32_t nchild,
                   float S, int may_split, uint2 *V, uint8_t *split, unsigned long long *visited, hipStream_t st)
 {
-    const dim3 grid = grid_stride_blocks(64ull * nblocks, DIST_MAX_WORKGROUPS), wg(OFFSET_THREADS);
-    switch (src.form) {
-    case FORM_GRID: hipLaunchKernelGGL((k_offset_level<CursorFT<false, false>>), grid, wg, 0, st, src.Q, D, mode, amount, blocks, nblocks, nchild, S, may_split, V, split, visited); break;
-    case FORM_SPLIT: hipLaunchKernelGGL((k_offset_level<CursorFT<false, true>>), grid, wg, 0, st, src.Q, D, mode, amount, blocks, nblocks, nchild, S, may_split, V, split, visited); break;
-    default: hipLaunchKernelGGL((k_offset_level<CursorG>), grid, wg, 0, st, src.Q, D, mode, amount, blocks, nblocks, nchild, S, may_split, V, split, visited); break;
-    }
+    const dim3 grid = grid_stride_blocks(64ull * nblocks, LEVEL_MAX_WORKGROUPS), wg(LEVEL_THREADS);
+    with_cursor(src.form, [&](auto c) {
+        hipLaunchKernelGGL((k_offset_level<typename decltype(c)::type>), grid, wg, 0, st, src.Q, D, mode, amount, blocks, nblocks, nchild, S, may_split, V, split, visited);
+    });
 }
 
 // The _device form's bitmap: one block per device, busy until the query that reads it has run.  It stays allocated for the life of
@@ -181,7 +175,7 @@ try {
         HIP_TRY(hipEventRecord(cs.ev[0], st));
         if (const int rc = launch_mark(src, opt->level, below, st)) return rc;
         const DistScene D{src.Q.nodes, src.Q.n_nodes, below, opt->level};
-        const auto level = [&](const OffsetBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
+        const auto level = [&](const LevelBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
             launch_level(src, D, mode, amount, blocks, nblocks, nchild, S, may_split, V, split, d_visited, st);
         };
         if (const int rc = build_levels(what, bufs, st, src.Q.n_nodes, depth, level, R)) return rc;

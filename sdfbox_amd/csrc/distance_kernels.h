@@ -1,7 +1,6 @@
 // The exact distance from a point to the surface a resident scene describes (gfx950): the nearest-surface search, the clearance
-// query built on it, and the level passes of offset and shell.  Included by distance.hip and, for the search, the level pass's body
-// and the two kernels the level loop launches (level_build.h), by blend.hip: k_dist_mark and k_offset_emit, which are not templates,
-// are `static` -- each of the two translation units has its own.  Host side, C ABI: distance.hip.
+// query built on it, and the value and level pass of offset and shell.  Included by distance.hip and, for the search, by blend.hip:
+// k_dist_mark, which is not a template, is `static` -- each of the two translation units has its own.  Host side, C ABI: distance.hip.
 //
 // Replaces: nothing in the reference's code -- its field is only ever read as stored, a distance in a thin band round the surface.
 //
@@ -17,10 +16,8 @@
 //   nearest_search  (b) one lane per point, depth first from the root, the children of a node nearest first; a child is skipped when
 //                   its bit is clear or its box cannot hold anything nearer than the best so far (box_gap2 and SEARCH_KEEP below: the
 //                   margin and its derivation); at a cut cell the lane recomputes the cell's triangles and folds tri_dist2 into the best
-//   k_offset_level  (c) place_kernels.h's k_place_level with value(p) = dist(p) - delta, or fabsf(dist(p)) - thickness / 2 (its body
-//                   is offset_level_body, a template on the value, which blend_kernels.h's k_blend_level instantiates too), and
-//   k_offset_emit   its k_place_emit: siblings, not shared definitions -- place_kernels.h's emit is not a template and belongs to
-//                   place.hip alone, and the placement's translation unit stays exactly as it was
+//   k_offset_level  (c) level_kernels.h's level_body with value(p) = dist(p) - delta, or fabsf(dist(p)) - thickness / 2; the rest
+//                   of a level (the scan, k_level_emit) is level_build.h's
 //   k_dist_query    (d) n points in, n sdfhip_clearance records out, a grid-stride loop over the same search
 //
 // The search's stack.  A lane that descends from a node keeps {the node's children block, the children not yet looked at} for its way
@@ -31,19 +28,13 @@
 // back shifts them out.
 #pragma once
 #include "query_kernels.h"   // QueryScene, grid_of, finite3, record_store; raymarch_device.h: the cursors, find_fresh, sample_after_find
-#include "sdf_bytes.h"       // from_float
-#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap
+#include "level_kernels.h"   // LevelBlock, LEVEL_THREADS, level_body
 #include "cell_tets.h"       // the cells, their tetrahedra and triangles, cut_position
 #include "tri_dist.h"        // tri_dist2
 
 namespace sdfhip {
 
 constexpr int DIST_THREADS = 256;
-constexpr int OFFSET_POINTS = 35;         // a block of eight siblings: the 27 corners of its 3x3x3 lattice and the 8 child centres
-constexpr int OFFSET_THREADS = 256;       // four waves, a block of siblings each: 32 nodes, one word of the split bitmap
-
-// A block's parent cell: its integer coordinates at its own depth (< 2^11), {x | y << 16, z} (the placement's OffsetBlock)
-typedef uint2 OffsetBlock;
 enum { OFFSET_GROW = 0, OFFSET_SHELL = 1 };                  // SDFHIP_OFFSET_* of include/sdfhip.h
 
 // what the search reads of the scene: the records, the bitmap of (a) -- ceil(n / 32) + 1 words, the last one zero -- and the level
@@ -255,62 +246,6 @@ __device__ __forceinline__ float dist_at(const QueryScene &Q, const DistScene &D
     return sign * sqrtf(best.d2);
 }
 
-// (c) k_place_level (place_kernels.h) with a value functor in place of place_value: the same blocks, lattice, shuffles, ballot and
-// stores.  One body for every level pass built on the exact distance: k_offset_level below and k_blend_level (blend_kernels.h)
-// instantiate it.  Value: SOURCES, the number of surfaces a point is searched against; value_of(px, py, pz, stk, seen) -> value(p),
-// which adds the records each search loaded to seen[0 .. SOURCES - 1]; value_of.visited, SOURCES counters in device memory: the
-// records the level's searches loaded, added up per block in 64 bits.  stack: the workgroup's MESH_MAX_DEPTH * OFFSET_THREADS entries.
-template <class Value>
-__device__ __forceinline__ void offset_level_body(const Value &value_of, const OffsetBlock *__restrict__ blocks, uint32_t nblocks, uint32_t nchild, float S,
-                                                  int may_split, uint2 *__restrict__ V, uint8_t *__restrict__ split, uint2 *stack)
-{
-    constexpr uint32_t WAVES = OFFSET_THREADS / 64;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t li = lane % 3u, lj = lane / 3u % 3u, lk = lane / 9u;           // the lattice corner of a lane < 27
-    const uint32_t c = lane & 7u, ci = c & 1u, cj = c >> 1 & 1u, ck = c >> 2;     // the child of a lane >= 27, and of a lane < 8
-    for (uint32_t b = blockIdx.x * WAVES + wave; b < nblocks; b += gridDim.x * WAVES) {
-        const OffsetBlock B = blocks[b];
-        const uint32_t bx = B.x & 0xFFFFu, by = B.x >> 16, bz = B.y;
-        // the root's block: the root's own eight corners and its centre
-        const bool wanted = nchild == 8u ? lane < (uint32_t)OFFSET_POINTS : lane < 27u ? (li < 2u && lj < 2u && lk < 2u) : lane == 27u;
-        float value = 0.0f;
-        uint32_t seen[Value::SOURCES] = {};
-        if (wanted) {
-            float px, py, pz;
-            if (lane < 27u) {
-                px = (float)(2u * bx + li) * S; py = (float)(2u * by + lj) * S; pz = (float)(2u * bz + lk) * S;
-            } else {
-                const uint32_t m = (lane - 27u) & 7u;
-                const float H = S * 0.5f;
-                px = (float)(2u * (2u * bx + (m & 1u)) + 1u) * H;
-                py = (float)(2u * (2u * by + (m >> 1 & 1u)) + 1u) * H;
-                pz = (float)(2u * (2u * bz + (m >> 2)) + 1u) * H;
-            }
-            value = value_of(px, py, pz, stack + threadIdx.x, seen);
-        }
-        uint32_t w[2] = { 0u, 0u };
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int src = (int)((ci + (uint32_t)(k & 1)) + 3u * (cj + (uint32_t)(k >> 1 & 1)) + 9u * (ck + (uint32_t)(k >> 2 & 1)));
-            w[k >> 2] |= from_float(__shfl(value, src), S) << (8 * (k & 3));
-        }
-        const float cv = fabsf(__shfl(value, 27 + (int)c));
-        const bool splits = lane < nchild && may_split && cv < 2.0f * S;
-        const unsigned long long mask = __ballot(splits);
-        if (lane < nchild) V[8ull * b + lane] = make_uint2(w[0], w[1]);
-        if (lane == 0) split[b] = (uint8_t)mask;
-        // the block's records, added once per block and source: a search may load up to n_nodes < 2^31 of them, so the wave's sum is
-        // made of the lanes' low and high 16 bits apart (each below 2^22) and put together in 64 bits
-#pragma unroll
-        for (int s = 0; s < Value::SOURCES; s++) {
-            uint32_t lo = seen[s] & 0xFFFFu, hi = seen[s] >> 16;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) { lo += (uint32_t)__shfl_xor((int)lo, o); hi += (uint32_t)__shfl_xor((int)hi, o); }
-            if (lane == 0 && (lo | hi)) atomicAdd(value_of.visited + s, ((unsigned long long)hi << 16) + lo);
-        }
-    }
-}
-
 // The offset's value.  mode: OFFSET_GROW value = dist - amount; OFFSET_SHELL value = fabsf(dist) - amount, amount = thickness * 0.5f
 // (the host's one multiplication).
 template <class CursorT> struct OffsetValue {
@@ -323,60 +258,19 @@ template <class CursorT> struct OffsetValue {
     __device__ __forceinline__ float operator()(float px, float py, float pz, uint2 *stk, uint32_t *seen) const
     {
         Nearest best;
-        const float dist = dist_at<CursorT, OFFSET_THREADS>(Q, D, px, py, pz, stk, best);
+        const float dist = dist_at<CursorT, LEVEL_THREADS>(Q, D, px, py, pz, stk, best);
         seen[0] = best.visited;
         return mode == OFFSET_SHELL ? fabsf(dist) - amount : dist - amount;
     }
 };
 
 template <class CursorT>
-__global__ __launch_bounds__(OFFSET_THREADS) void k_offset_level(QueryScene Q, DistScene D, int mode, float amount, const OffsetBlock *__restrict__ blocks,
+__global__ __launch_bounds__(LEVEL_THREADS) void k_offset_level(QueryScene Q, DistScene D, int mode, float amount, const LevelBlock *__restrict__ blocks,
                                                                 uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *__restrict__ V,
                                                                 uint8_t *__restrict__ split, unsigned long long *__restrict__ visited)
 {
-    __shared__ uint2 stack[MESH_MAX_DEPTH * OFFSET_THREADS];
-    offset_level_body(OffsetValue<CursorT>{Q, D, mode, amount, visited}, blocks, nblocks, nchild, S, may_split, V, split, stack);
-}
-
-// The split bitmap of a level of n nodes, words 0 .. ceil(n / 32) - 1, to k_rank_scan_words (scan_device.h): the bits from n on
-// were never written
-struct OffsetSplitWords {
-    const uint32_t *split;
-    uint32_t n;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const
-    {
-        const uint32_t rest = n - 32u * i;
-        return rest >= 32u ? split[i] : split[i] & ((1u << rest) - 1u);
-    }
-};
-
-// Pass 2 of a level (its n nodes; the result's nodes first .. first + n - 1), as the placement's: eight lanes per node, lane i the
-// node's child i.  A splitting node of rank r (the splits before it in the level's order) gets the block first + n + 8 r, appended
-// behind the level: its children link, the eight children's {parent, -1}, and the next level's block r with the node's own
-// coordinates.  cap_out / cap_next: the room in links[] and next[].
-static __global__ __launch_bounds__(256) void k_offset_emit(const OffsetBlock *__restrict__ blocks, uint32_t n, uint32_t nchild, uint32_t first,
-                                                     const uint32_t *__restrict__ split, const uint32_t *__restrict__ pre,
-                                                     const uint32_t *__restrict__ chunk, int2 *__restrict__ links, uint32_t cap_out,
-                                                     OffsetBlock *__restrict__ next, uint32_t cap_next)
-{
-    const uint64_t total = 8ull * n;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t t = (uint32_t)(j >> 3), i = (uint32_t)j & 7u;
-        const uint32_t word = split[t >> 5];
-        if (!((word >> (t & 31u)) & 1u)) continue;
-        const uint32_t r = rank_in_bitmap(chunk, pre, t >> 5, word, t & 31u);
-        const uint32_t self = first + t;
-        const uint64_t child = (uint64_t)first + n + 8ull * r + i;
-        if (child >= cap_out || r >= cap_next) continue;                       // (a guard: the host sized both from the scan's total)
-        links[child] = make_int2((int32_t)self, -1);
-        if (i == 0) {
-            links[self].y = (int32_t)child;
-            const OffsetBlock B = blocks[nchild == 8u ? t >> 3 : 0u];
-            const uint32_t c = nchild == 8u ? t & 7u : 0u;
-            const uint32_t x = 2u * (B.x & 0xFFFFu) + (c & 1u), y = 2u * (B.x >> 16) + (c >> 1 & 1u), z = 2u * B.y + (c >> 2);
-            next[r] = make_uint2(x | y << 16, z);
-        }
-    }
+    __shared__ uint2 stack[MESH_MAX_DEPTH * LEVEL_THREADS];
+    level_body(OffsetValue<CursorT>{Q, D, mode, amount, visited}, blocks, nblocks, nchild, S, may_split, V, split, stack + threadIdx.x);
 }
 
 // (d) xyz: n x 3 floats, packed; out: n sdfhip_clearance records as two uint4 {distance, node, nearest.x, nearest.y | nearest.z,

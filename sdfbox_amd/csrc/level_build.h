@@ -1,10 +1,11 @@
-// The host side that the tree builders on the exact distance share: distance.hip (sdfhip_scene_offset) and blend.hip
-// (sdfhip_scene_blend).  What a call reads of a handle and refuses of it, the "surface below" bitmap's launch, and the level loop
-// (build_levels: a template on the launch of a level's first pass, so each caller brings its own kernel; the shared bitmap scan and
-// k_offset_emit do the rest).  Everything here is inline or a template; the two kernels it launches are distance_kernels.h's static
-// ones.  place.hip keeps its own copy of the loop: that translation unit stays as it was.
+// The host side that every lattice builder shares: place.hip (sdfhip_scene_place), distance.hip (sdfhip_scene_offset) and blend.hip
+// (sdfhip_scene_blend).  What a call reads of a handle, the cursor a look-up takes, and the level loop (build_levels: a template on
+// the launch of a level's first pass, so each caller brings its own kernel round level_kernels.h's level_body; the shared bitmap
+// scan and k_level_emit do the rest).  Everything here is inline or a template.  What only the builders on the exact distance need
+// -- their refusals, the "surface below" bitmap -- is distance_host.h's.
 #pragma once
-#include "distance_kernels.h"
+#include "level_kernels.h"
+#include "query_kernels.h"   // QueryScene; raymarch_device.h: the cursors
 #include "host_support.h"
 
 #include <algorithm>
@@ -14,11 +15,11 @@
 namespace sdfhip {
 namespace levels {
 
-constexpr int MAX_DEVICES = 64;
-constexpr uint32_t DIST_MAX_WORKGROUPS = 2048;      // every pass strides with at most this many workgroups of four waves: 8 waves on each of the 1024 SIMDs
+constexpr uint32_t LEVEL_MAX_WORKGROUPS = 2048;     // every pass strides with at most this many workgroups of four waves: 8 waves on each of the 1024 SIMDs
 
-// The sign's look-up takes the march's cursor, as the placement's value does: the grid wherever the handle has a full-depth one,
-// else the walk along the links.  Both give the same bytes.
+// Which cursor a look-up takes: no cell index is wanted, so the choice is the march's (query.hip's form_of for a march): the grid
+// wherever the handle has a full-depth one -- dense, or coarse level + fine blocks -- else the shader's walk along the links.  All
+// give the same bytes.
 enum Form { FORM_GENERIC = 0, FORM_GRID = 1, FORM_SPLIT = 2 };
 inline Form form_of(const sdfhip_scene *s)
 {
@@ -30,7 +31,20 @@ inline QueryScene scene_of(const sdfhip_scene *s)
     return QueryScene{s->nodes, s->n, s->d_top, s->d_fine, s->top_level, s->fine_bits};
 }
 
-// what a call reads of the handle, under its lock
+// f(CursorOf<C>{}) with C the cursor of the form: a kernel that is a template on the cursor is launched as
+// k<typename decltype(c)::type>
+template <class CursorT> struct CursorOf { using type = CursorT; };
+template <class F> void with_cursor(Form form, F f)
+{
+    switch (form) {
+    case FORM_GRID: f(CursorOf<CursorFT<false, false>>{}); break;
+    case FORM_SPLIT: f(CursorOf<CursorFT<false, true>>{}); break;
+    default: f(CursorOf<CursorG>{}); break;
+    }
+}
+
+// What a call reads of the handle, under its lock, which is released before any work is issued: the records and the grids are fixed
+// at upload and only ever read, so renders, queries and meshes of the source on other threads do not wait for the builder.
 struct Source {
     QueryScene Q;
     Form form;
@@ -42,31 +56,6 @@ inline Source read_source(sdfhip_scene *s)
     std::lock_guard<std::mutex> lk(s->lock);
     return Source{scene_of(s), form_of(s), s->depth, s->device, s->stack_ok};
 }
-// sdfhip_scene_mesh's refusal: the surface is its triangles
-inline int check_source(const char *what, const Source &src)
-{
-    if (!src.stack_ok || src.depth > (uint32_t)MESH_MAX_DEPTH)
-        return fail(SDFHIP_ERR_BAD_TREE, "%s: the tree is not consistent (or deeper than %d levels): it has no mesh, so no surface to measure from", what,
-                    MESH_MAX_DEPTH);
-    if (src.device < 0 || src.device >= MAX_DEVICES) return fail(SDFHIP_ERR_ARG, "%s: device %d", what, src.device);
-    return SDFHIP_OK;
-}
-inline int check_level(const char *what, int32_t level)
-{
-    if (level < -1 || level > MESH_MAX_DEPTH) return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, level, MESH_MAX_DEPTH);
-    return SDFHIP_OK;
-}
-
-inline size_t bitmap_words(uint32_t n) { return ((size_t)n + 31) / 32 + 1; }     // (+ 1: sibling_bits reads one word past a block's first)
-
-// (a) on `st`: the bitmap zeroed and marked
-inline int launch_mark(const Source &src, int32_t level, uint32_t *below, hipStream_t st)
-{
-    HIP_TRY(hipMemsetAsync(below, 0, bitmap_words(src.Q.n_nodes) * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_dist_mark, grid_stride_blocks(src.Q.n_nodes, DIST_MAX_WORKGROUPS), dim3(DIST_THREADS), 0, st, src.Q.nodes, src.Q.n_nodes, (int)level, below);
-    HIP_TRY(hipGetLastError());
-    return SDFHIP_OK;
-}
 
 struct LevelBuild {
     int2 *dS = nullptr;            // the result's links and bytes, in `bufs`
@@ -75,13 +64,15 @@ struct LevelBuild {
     uint64_t points = 0;           // 9 for the root and 35 for every block of eight siblings
 };
 
-// The level loop, as place.hip runs it for the placement (a sibling: that translation unit stays as it was), moved here from
-// distance.hip unchanged.
-// what: the entry point's name for the messages.  nodes_in: the source's size, which the arrays start from.  launch_level(blocks,
-// nblocks, nchild, S, may_split, V, split): launches the level's first pass on `st`.  Throws NoMem (DeviceBuffers).  The last
-// level may still be in flight on `st` when it returns: the caller waits.
+// The level loop.  what: the entry point's name for the messages.  nodes_in: the source's size, which the arrays start from.
+// launch_level(blocks, nblocks, nchild, S, may_split, V, split): launches the level's first pass on `st`.  started: if given,
+// recorded on `st` once the first arrays are allocated and the root is queued, before the first level (the placement's kernel_ms
+// starts there: the allocations' host time is not part of it).  Allocates, in this order, dS, dV, the blocks, split, pre, chunk, then
+// the next level's blocks and whatever grows.  Throws NoMem (DeviceBuffers).  The last level may still be in flight on `st` when it
+// returns: the caller waits.
 template <class LaunchLevel>
-int build_levels(const char *what, DeviceBuffers &bufs, hipStream_t st, uint32_t nodes_in, int depth, LaunchLevel launch_level, LevelBuild &R)
+int build_levels(const char *what, DeviceBuffers &bufs, hipStream_t st, uint32_t nodes_in, int depth, LaunchLevel launch_level, LevelBuild &R,
+                 hipEvent_t started = nullptr)
 {
     // The result's arrays start with room for a tree of the source's size and double when a level does not fit: the levels
     // already written are copied over.  The per-level buffers are sized for what the arrays can hold -- a level is part of the
@@ -108,12 +99,13 @@ int build_levels(const char *what, DeviceBuffers &bufs, hipStream_t st, uint32_t
         return SDFHIP_OK;
     };
     const auto words_of = [](size_t nodes) { return (nodes + 31) / 32; };
-    OffsetBlock *cur = nullptr, *next = nullptr;
+    LevelBlock *cur = nullptr, *next = nullptr;
     uint32_t *split = nullptr, *pre = nullptr, *chunk = nullptr;
     size_t cur_cap = 0, next_cap = 0, split_cap = 0, pre_cap = 0, chunk_cap = 0;
     if (const int rc = room(cur, cur_cap, cap / 8 + 1)) return rc;
-    HIP_TRY(hipMemsetAsync(cur, 0, sizeof(OffsetBlock), st));                 // the root's block: the cell at the origin
+    HIP_TRY(hipMemsetAsync(cur, 0, sizeof(LevelBlock), st));                  // the root's block: the cell at the origin
     HIP_TRY(hipMemsetAsync(R.dS, 0xFF, sizeof(int2), st));                   // the root: {-1, -1}
+    if (started) HIP_TRY(hipEventRecord(started, st));
 
     uint32_t first = 0, n = 1, nblocks = 1, nchild = 1;
     for (int d = 0;; d++) {
@@ -127,9 +119,9 @@ int build_levels(const char *what, DeviceBuffers &bufs, hipStream_t st, uint32_t
         idle = false;
         launch_level(cur, nblocks, nchild, S, may_split, R.dV + first, reinterpret_cast<uint8_t *>(split));
         HIP_TRY(hipGetLastError());
-        R.points += nchild == 1 ? 9u : (uint64_t)OFFSET_POINTS * nblocks;
+        R.points += nchild == 1 ? 9u : (uint64_t)LEVEL_POINTS * nblocks;
         if (!may_split) break;
-        hipLaunchKernelGGL(k_rank_scan_words<OffsetSplitWords>, dim3(nchunk), dim3(256), 0, st, OffsetSplitWords{ split, n }, m, pre, chunk);
+        hipLaunchKernelGGL(k_rank_scan_words<LevelSplitWords>, dim3(nchunk), dim3(256), 0, st, LevelSplitWords{ split, n }, m, pre, chunk);
         hipLaunchKernelGGL(k_rank_scan_chunks<true>, dim3(1), dim3(1024), 0, st, chunk, nchunk);
         HIP_TRY(hipGetLastError());
         uint32_t n_split = 0;
@@ -148,7 +140,7 @@ int build_levels(const char *what, DeviceBuffers &bufs, hipStream_t st, uint32_t
         }
         if (const int rc = room(next, next_cap, cap / 8 + 1)) return rc;
         idle = false;
-        hipLaunchKernelGGL(k_offset_emit, grid_stride_blocks(8ull * n, DIST_MAX_WORKGROUPS), dim3(256), 0, st, cur, n, nchild, first, split, pre,
+        hipLaunchKernelGGL(k_level_emit, grid_stride_blocks(8ull * n, LEVEL_MAX_WORKGROUPS), dim3(256), 0, st, cur, n, nchild, first, split, pre,
                            chunk, R.dS, (uint32_t)cap, next, n_split);
         HIP_TRY(hipGetLastError());
         std::swap(cur, next);

@@ -155,7 +155,7 @@ def test_offset_bytes_on_a_result_whose_arrays_grow(sb):
     src, case = BIG
     S, V, counts = restated(src, *case)
     level_sizes = [len(level) for level in pr.levels(S)]
-    # the offset's own copy of the level loop where a small case does not reach: arrays that had to grow six times (they start at
+    # the level loop under the offset's first pass where a small case does not reach: arrays that had to grow six times (they start at
     # 4096 nodes), a level that the first pass takes in more than one sweep of its grid (65 536 nodes), level lists that end inside
     # a workgroup (32 nodes).  (No level that is SCANNED is past the scan's chunk of 32 768 nodes: the last level is not scanned, and
     # a level behind such a level costs the brute force 20 s.  DESIGN.md N13 says so.)
