@@ -1,8 +1,10 @@
-"""Trees built to break a consumer, shared by the tests of the renderer, the queries, the mesh and the edit.  A plain helper module
+"""Trees built to break a consumer, shared by the tests of the renderer, the queries, the mesh, the edit, the prune, the combination,
+the placement and the measure.  A plain helper module
 (like the *_restatement.py files): generators of consistent trees that no builder would lay out -- depth-first order, a chain along
 one corner, blocks appended under randomly chosen leaves, node counts one past a kernel's chunk, row and wave -- byte fillers that are
-no distance field, the named trees `zoo()` every zoo test uses, and the edit cases of tests/test_tree_zoo.py and
-tests/test_gpu_tree_zoo.py with a cache of their restated results.
+no distance field, the named trees `zoo()` every zoo test uses, the edit cases of tests/test_tree_zoo.py and
+tests/test_gpu_tree_zoo.py and the prune, combine, place and measure cases of tests/test_zoo_builders.py and
+tests/test_gpu_zoo_builders.py, with a cache of their restated results.
 
 _random_tree and _chain_tree are the generators of tests/test_gpu_parity.py, moved here unchanged: their code and the order of their
 RNG draws are what the parity fuzz seeds (the pinned seed 26 included) were found with."""
@@ -12,7 +14,7 @@ import edit_restatement as er
 
 LEAF_BYTES = [60, 80, 90, 120, 70, 200, 40, 255]           # the single leaf of test_degenerate_and_deep_trees
 BLOCK_COUNTS = (8, 32, 127, 128, 256, 512)                  # 1 + 8k = 65, 257, 1017, 1025, 2049, 4097 nodes
-NODE_CAP = 400_000                                          # no restated edit result may be larger
+NODE_CAP = 400_000                                          # no restated result (edit, prune, combine, place) may be larger
 
 
 def _random_tree(rng, max_depth, p_split, max_nodes=60000):
@@ -198,6 +200,12 @@ def restated(key, make):
     return _restated[key]
 
 
+def walked(name):
+    """mr.walk of the zoo tree `name` (every node's depth and coordinates), cached"""
+    import mesh_restatement as mr
+    return restated(("walk", name), lambda: mr.walk(zoo()[name][0]))
+
+
 def restated_edit(name, edits, max_depth, start=None):
     """er.edit on the zoo tree `name` (or on the arrays `start` = (key, structs, values)), cached"""
     if start is None:
@@ -219,3 +227,72 @@ def restated_chain(name):
     second = restated_edit(name, [b], md_b, start=("after A", first[0], first[1]))
     as_list = restated_edit(name, [a, b], md_b)
     return first, second, as_list
+
+
+# ---- the cases of prune, combine, place and measure (tests/test_zoo_builders.py, tests/test_gpu_zoo_builders.py) ------------------
+# None of the four restatements was written with these trees in view; each answer is made once and shared, as the edits' are.
+PRUNE_TOLERANCES = (0, 8, 255)
+COMBINE_DEPTHS = (-1, 3)
+# (a, b): two depth-first trees; append order against depth-first order; a shallow wide tree against the 12-deep chain; one node
+# against a tree; one handle as both operands
+COMBINE_PAIRS = [("dfs_d6_a", "dfs_d6_b"), ("blocks_4097", "dfs_d6_a"), ("blocks_1025", "chain12"), ("leaf", "blocks_257"),
+                 ("chain12", "chain12")]
+COMBINE_REVERSED = [("dfs_d6_a", "blocks_4097")]            # the difference is not symmetric: this pair the other way round too
+# source -> the depths it is placed to.  Never the source's own: random bytes cut nearly every leaf, and a placement to depth 7 or 12
+# would have millions of nodes.  The deeper ones grow the level builder's arrays (1.5 times the source at first) more than once.
+PLACE_DEPTHS = {"leaf": (4,), "chain12": (4, 6), "blocks_65": (4, 5), "blocks_1025": (4,), "dfs_d6_a": (4, 6)}
+PLACE_NAMES = ("identity", "dyadic_075", "generic_half")
+PLACE_EXTRA = [("blocks_1025", "identity", 6)]              # 110 489 nodes from 1025
+
+
+def prune_depths(depth):
+    """no cut, the root alone, one level inside the tree"""
+    return sorted({-1, 0, max(depth - 1, 0)})
+
+
+def combine_cases():
+    """[(a, b, op, max_depth)]: every pair under every operation and cut, and the reversed pair under the difference"""
+    import combine_restatement as cr
+    out = [(a, b, op, md) for a, b in COMBINE_PAIRS for op in cr.OPS for md in COMBINE_DEPTHS]
+    return out + [(a, b, cr.COMBINE_SUBTRACT, md) for a, b in COMBINE_REVERSED for md in COMBINE_DEPTHS]
+
+
+def place_cases(src=None):
+    """[(source, placement, depth)] (of one source, if given)"""
+    out = [(s, name, d) for s, depths in PLACE_DEPTHS.items() for name in PLACE_NAMES for d in depths] + PLACE_EXTRA
+    return [c for c in out if src is None or c[0] == src]
+
+
+def place_args(name):
+    """(R, s, t): the identity; a dyadic scale and translation (a look-up lands on a lattice of the source four times finer than the
+    result's); the generic two-axis rotation at half size about the cube's centre of tests/test_gpu_place.py"""
+    import place_restatement as plr
+    if name == "identity":
+        return plr.IDENTITY, 1.0, (0.0, 0.0, 0.0)
+    if name == "dyadic_075":
+        return plr.IDENTITY, 0.75, (0.125, 0.0, 0.25)
+    assert name == "generic_half"
+    import sdfbox_amd
+    return sdfbox_amd.placement(30, 20, 0, 0.5)
+
+
+def restated_prune(name, tolerance, max_depth):
+    import prune_restatement as pr
+    return restated(("prune", name, tolerance, max_depth), lambda: pr.prune(*zoo()[name], tolerance, max_depth))
+
+
+def restated_combine(a, b, op, max_depth):
+    """(structs, values, counts)"""
+    import combine_restatement as cr
+    return restated(("combine", a, b, op, max_depth), lambda: cr.combine(zoo()[a], zoo()[b], op, max_depth, want_counts=True))
+
+
+def restated_place(src, name, depth):
+    """(structs, values, counts)"""
+    import place_restatement as plr
+    return restated(("place", src, name, depth), lambda: plr.place(zoo()[src], *place_args(name), depth, want_counts=True))
+
+
+def restated_measure(name, level):
+    import measure_restatement as ms
+    return restated(("measure", name, level), lambda: ms.measure(*zoo()[name], level, walked=walked(name)))
