@@ -237,6 +237,30 @@ public:
         sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
+    // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at
+    // index (k * ny + j) * nx + i and at origin + (i, j, k) * spacing in the unit cube's coordinates, stored value * value_scale =
+    // distance -- the trilinear interpolant, continued outside the lattice's box at slope 1; it replaces the loaded model as a Load
+    // does.  A non-finite sample is refused; nothing is pruned (chain Prune).  Volume: the loaded model's distances on such a lattice
+    // (n_a >= 1), x fastest.  host_out (may be null): the result's host arrays
+    void LoadVolume(const std::vector<float> &grid, const uint32_t (&n)[3], const float (&origin)[3], float spacing, int depth,
+                    float value_scale = 1.0f, sdfhip_volume_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        if ((uint64_t)n[0] * n[1] * n[2] != grid.size()) throw Error(SDFHIP_ERR_ARG, "LoadVolume: the grid's size is not nx * ny * nz");
+        const sdfhip_volume vol = Lattice(n, origin, spacing, value_scale, depth);
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_volume_build(device, grid.data(), &vol, &fresh, host_out, stats));
+        if (scene) sdfhip_scene_free(scene);
+        scene = fresh;
+    }
+    std::vector<float> Volume(const uint32_t (&n)[3], const float (&origin)[3], float spacing)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Volume: no model loaded");
+        const sdfhip_volume lattice = Lattice(n, origin, spacing, 0.0f, 0);
+        std::vector<float> out((size_t)n[0] * n[1] * n[2]);
+        Check(sdfhip_scene_volume(scene, &lattice, out.data()));
+        return out;
+    }
     // Exact distance (sdfhip_scene_distance / sdfhip_scene_offset; nothing in the reference corresponds).  Distance: how far points
     // (xyz: 3 floats per point) are from the loaded model's surface -- the triangles of its mesh at `level` -- at any range, where
     // Sample's distance saturates a leaf edge away; a bad element gets SDFHIP_QUERY_INVALID, not an exception.  Offset: the model grown
@@ -372,6 +396,17 @@ public:
     }
 
 private:
+    static sdfhip_volume Lattice(const uint32_t (&n)[3], const float (&origin)[3], float spacing, float value_scale, int depth)
+    {
+        sdfhip_volume v = {};
+        v.size = (uint32_t)sizeof(sdfhip_volume);
+        for (int a = 0; a < 3; a++) { v.n[a] = n[a]; v.origin[a] = origin[a]; }
+        v.spacing = spacing;
+        v.value_scale = value_scale;
+        v.dtype = SDFHIP_VOLUME_F32;
+        v.depth = depth;
+        return v;
+    }
     void OffsetAs(int32_t mode, float amount, int depth, int level, sdfhip_offset_stats *stats, sdfhip_octdata *host_out, const char *unloaded)
     {
         if (!scene) throw Error(SDFHIP_ERR_ARG, unloaded);

@@ -47,13 +47,14 @@ BRUSH_SPHERE, BRUSH_BOX = 0, 1
 COMBINE_UNION, COMBINE_INTERSECT, COMBINE_SUBTRACT = 0, 1, 2      # sdfhip_scene_combine: A or B, A and B, A without B
 OFFSET_GROW, OFFSET_SHELL = 0, 1     # sdfhip_scene_offset: dist - amount / fabsf(dist) - amount / 2
 BLEND_UNION, BLEND_INTERSECT, BLEND_SUBTRACT, BLEND_MORPH = 0, 1, 2, 3      # sdfhip_scene_blend: smooth A or B, A and B, A without B; the in-between
+VOLUME_F32, VOLUME_F16 = 0, 1        # sdfhip_volume.dtype
 QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdfhip_probe.status / sdfhip_hit.status
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -217,6 +218,33 @@ else:
 
 
     assert (ctypes.sizeof(Placement), ctypes.sizeof(PlaceStats)) == (60, 40)
+
+
+    class Volume(ctypes.Structure):
+        """sdfhip_volume: a regular lattice of n = (nx, ny, nz) samples, sample (i, j, k) at origin + (i, j, k) * spacing and at index
+        (k * ny + j) * nx + i.  value_scale and depth describe a build (stored value * value_scale = distance in cube units; depth
+        0..12) and are 0 for a lattice to fill; dtype VOLUME_F32 / VOLUME_F16."""
+        _fields_ = [("size", ctypes.c_uint32), ("n", ctypes.c_uint32 * 3), ("origin", ctypes.c_float * 3), ("spacing", ctypes.c_float),
+                    ("value_scale", ctypes.c_float), ("dtype", ctypes.c_int32), ("depth", ctypes.c_int32)]
+
+        def __init__(self, n=(2, 2, 2), origin=(0, 0, 0), spacing=1.0, value_scale=0.0, dtype=0, depth=0):
+            n = [int(x) for x in n]
+            o = [float(x) for x in origin]
+            if len(n) != 3 or len(o) != 3:
+                raise ValueError("n and origin must have three components")
+            if any(x < 0 or x > 0xFFFFFFFF for x in n):
+                raise ValueError("n must be three counts")
+            super().__init__(ctypes.sizeof(type(self)), (ctypes.c_uint32 * 3)(*n), (ctypes.c_float * 3)(*o), float(spacing), float(value_scale),
+                             int(dtype), int(depth))
+
+
+    class VolumeStats(ctypes.Structure):
+        _fields_ = [("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("pad_", ctypes.c_uint32),
+                    ("samples", ctypes.c_uint64), ("check_ms", ctypes.c_float), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float),
+                    ("total_ms", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(Volume), ctypes.sizeof(VolumeStats)) == (44, 40)
 
 
     class Clearance(ctypes.Structure):
@@ -436,6 +464,10 @@ _SIG = {
     "sdfhip_scene_prune": (_c.c_int, [_vp, _c.POINTER(PruneOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PruneStats)]),
     "sdfhip_scene_combine": (_c.c_int, [_vp, _vp, _c.c_int32, _c.POINTER(CombineOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(CombineStats)]),
     "sdfhip_scene_place": (_c.c_int, [_vp, _c.POINTER(Placement), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PlaceStats)]),
+    "sdfhip_volume_build": (_c.c_int, [_c.c_int, _vp, _c.POINTER(Volume), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(VolumeStats)]),
+    "sdfhip_volume_build_device": (_c.c_int, [_c.c_int, _vp, _c.POINTER(Volume), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(VolumeStats)]),
+    "sdfhip_scene_volume": (_c.c_int, [_vp, _c.POINTER(Volume), _vp]),
+    "sdfhip_scene_volume_device": (_c.c_int, [_vp, _c.POINTER(Volume), _vp, _vp]),
     "sdfhip_scene_distance": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_int32, _vp]),
     "sdfhip_scene_distance_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_int32, _vp, _vp]),
     "sdfhip_scene_offset": (_c.c_int, [_vp, _c.POINTER(OffsetOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(OffsetStats)]),

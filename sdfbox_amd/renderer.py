@@ -94,6 +94,16 @@ def placement_fit(measure, yaw=0, pitch=0, roll=0, size=0.8, to=(0.5, 0.5, 0.5))
     return placement(yaw, pitch, roll, float(size) / side, about=(lo + hi) * 0.5, to=to)
 
 
+def lattice_of_depth(d):
+    """(shape, origin, spacing) for Scene.Volume / Scene.FromVolume: the lattice whose vertices are every corner and every inner
+    centre of a tree of depth d -- 2^d + 1 samples along each axis, from the origin, 2^-d apart (every point a build to depth d
+    evaluates is a vertex of it, and vertices are exact)."""
+    d = int(d)
+    if not 0 <= d <= 11:
+        raise ValueError("lattice_of_depth: depth outside 0..11 (a lattice has at most 4096 samples along an axis)")
+    return ((2 ** d + 1,) * 3, (0, 0, 0), 2.0 ** -d)
+
+
 class Scene:
     """A scene resident in one GPU's HBM (replaces the `data` / `values`
     bindings of Program.cs:147-152)."""
@@ -234,6 +244,113 @@ class Scene:
         if want_stats:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
+
+    # -- volumes in and out (sdfhip_volume_build / sdfhip_scene_volume): a dense lattice of distances as a scene and back -------------
+    @classmethod
+    def FromVolume(cls, grid, origin=(0, 0, 0), spacing=None, depth=None, value_scale=1.0, device=0, want_octdata=False, want_stats=False):
+        """A scene from a regular lattice of distances (sdfhip_volume_build[_device]): `grid` is a C-contiguous (nz, ny, nx) numpy
+        array, or a contiguous torch tensor on cuda:`device` (read where it lies, through data_ptr(), after the device's current
+        torch stream has been waited for), float32 or float16, at least two samples along each axis.  Sample (k, j, i) sits at origin
+        + (i, j, k) * spacing in the unit cube's coordinates; spacing None = the grid spans the cube along x, 1 / (nx - 1).
+        stored value * value_scale = distance in cube units (a field in voxel units: value_scale = spacing; positive inside: a
+        negative scale).  depth: 0..12, the deepest level of the tree; None = the first level whose cells are no larger than the
+        spacing.  The value is the trilinear interpolant, continued outside the grid's box at slope 1; the split rule assumes a
+        distance, so a truncated field splits everywhere below its truncation: chain Prune.  A non-finite sample is refused
+        (ERR_ARG).  want_octdata: also the result's host arrays; want_stats: a VolumeStats."""
+        from .octdata import OctData
+        dtypes = {"float32": _lib.VOLUME_F32, "float16": _lib.VOLUME_F16}
+        on_device = hasattr(grid, "data_ptr") and hasattr(grid, "is_cuda")
+        if on_device:
+            import torch
+            name = str(grid.dtype).replace("torch.", "")
+            if not grid.is_cuda:
+                raise TypeError("FromVolume: a torch tensor must live on the device (a host tensor: pass tensor.numpy())")
+            if name not in dtypes:
+                raise TypeError(f"FromVolume: dtype {grid.dtype} is neither float32 nor float16")
+            if grid.dim() != 3 or not grid.is_contiguous():
+                raise ValueError("FromVolume: the grid must be a contiguous (nz, ny, nx) tensor")
+            if grid.device.index != int(device):
+                raise ValueError(f"FromVolume: the tensor is on {grid.device}, the scene is asked for on device {int(device)}")
+            shape = tuple(int(x) for x in grid.shape)
+        elif isinstance(grid, np.ndarray):
+            name = grid.dtype.name
+            if name not in dtypes:
+                raise TypeError(f"FromVolume: dtype {grid.dtype} is neither float32 nor float16")
+            if grid.ndim != 3 or not grid.flags.c_contiguous:
+                raise ValueError("FromVolume: the grid must be a C-contiguous (nz, ny, nx) array")
+            shape = grid.shape
+        else:
+            raise TypeError("FromVolume: the grid must be a numpy array or a torch tensor on the device")
+        nz, ny, nx = shape
+        if min(shape) < 2 or max(shape) > 4096 or nx * ny * nz > 2 ** 31:
+            raise ValueError(f"FromVolume: a grid of {nx} x {ny} x {nz} samples (2..4096 along each axis, at most 2^31 in all)")
+        spacing = 1.0 / (nx - 1) if spacing is None else float(spacing)
+        if not (np.isfinite(spacing) and spacing > 0):
+            raise ValueError("FromVolume: spacing must be a finite number above 0")
+        if depth is None:
+            depth = min(max(int(np.ceil(-np.log2(spacing))), 0), 12)
+        if not 0 <= int(depth) <= 12:
+            raise ValueError("FromVolume: depth outside 0..12")
+        vol = _lib.Volume((nx, ny, nz), origin, spacing, value_scale, dtypes[name], depth)
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.device = int(device)
+        raw = _lib.COctData()
+        st = _lib.VolumeStats()
+        if on_device:
+            torch.cuda.current_stream(self.device).synchronize()
+            check(lib.sdfhip_volume_build_device(self.device, ctypes.c_void_p(grid.data_ptr()), ctypes.byref(vol), ctypes.byref(self._h),
+                                                 ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        else:
+            check(lib.sdfhip_volume_build(self.device, grid.ctypes.data, ctypes.byref(vol), ctypes.byref(self._h),
+                                          ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        self._describe()
+        out = [self]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def Volume(self, shape, origin=(0, 0, 0), spacing=None, dtype=np.float32, out=None):
+        """This scene's distances on a regular lattice (sdfhip_scene_volume[_device]): element (k, j, i) of the (nz, ny, nx) = `shape`
+        result is what Sample returns at origin + (i, j, k) * spacing clamped to the cube, plus the distance from there to the point:
+        the field continued outside the cube at slope 1.  spacing None = the lattice spans the cube along x, 1 / (nx - 1).  Returns
+        a numpy array of `dtype` (float32 or float16); or, with `out` a contiguous torch tensor of that shape on this scene's device,
+        fills it asynchronously on the device's current torch stream and returns it.  lattice_of_depth(d) gives the three arguments
+        of the lattice a depth-d tree is built on."""
+        dtypes = {"float32": _lib.VOLUME_F32, "float16": _lib.VOLUME_F16}
+        shape = tuple(int(x) for x in shape)
+        if len(shape) != 3 or min(shape) < 1 or max(shape) > 4096 or shape[0] * shape[1] * shape[2] > 2 ** 31:
+            raise ValueError(f"Volume: shape {shape} is not (nz, ny, nx) with 1..4096 along each axis and at most 2^31 elements")
+        nz, ny, nx = shape
+        if spacing is None:
+            if nx < 2:
+                raise ValueError("Volume: a lattice of one sample along x needs a spacing")
+            spacing = 1.0 / (nx - 1)
+        if not (np.isfinite(float(spacing)) and float(spacing) > 0):
+            raise ValueError("Volume: spacing must be a finite number above 0")
+        if out is None:
+            name = np.dtype(dtype).name
+            if name not in dtypes:
+                raise TypeError(f"Volume: dtype {dtype} is neither float32 nor float16")
+            lattice = _lib.Volume((nx, ny, nz), origin, spacing, 0.0, dtypes[name], 0)
+            res = np.empty(shape, dtype=np.dtype(dtype))
+            check(lib.sdfhip_scene_volume(self._h, ctypes.byref(lattice), res.ctypes.data))
+            return res
+        if not (hasattr(out, "data_ptr") and hasattr(out, "is_cuda")):
+            raise TypeError("Volume: out must be a torch tensor on the scene's device")
+        import torch
+        name = str(out.dtype).replace("torch.", "")
+        if not out.is_cuda or name not in dtypes:
+            raise TypeError("Volume: out must be a float32 or float16 tensor on the scene's device")
+        if tuple(out.shape) != shape or not out.is_contiguous() or out.device.index != self.device:
+            raise ValueError(f"Volume: out must be a contiguous tensor of shape {shape} on device {self.device}")
+        lattice = _lib.Volume((nx, ny, nz), origin, spacing, 0.0, dtypes[name], 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib.sdfhip_scene_volume_device(self._h, ctypes.byref(lattice), ctypes.c_void_p(out.data_ptr()),
+                                             ctypes.c_void_p(int(stream)) if stream else None))
+        return out
 
     # -- exact distance (sdfhip_scene_distance / _offset): clearance, offset and shell ------------------------------------------------
     def Distance(self, points, level=-1):
