@@ -237,6 +237,40 @@ public:
         sdfhip_scene_free(scene);
         scene = fresh;
     }
+    // Composition (sdfhip_scene_compose): the model becomes ONE tree made of many placed instances of the models that Programs on
+    // this device have loaded (this one may be among them, and the same Program may appear in many parts), in a single pass: part
+    // k's own field under its own placement -- a point x of it lands at scale * R x + t, as Place's -- folded in float in list order
+    // (SDFHIP_COMBINE_UNION min, _INTERSECT max, _SUBTRACT max with the negated value; the first part is a union) and rounded to a
+    // byte once.  One part is Place byte for byte; the result is not Combine of Places (one quantisation, not two).  depth: -1 = the
+    // largest depth among the parts' models, else 0..12.  The result replaces the loaded model as Place's does; the other Programs
+    // keep theirs.  Nothing is pruned (chain Prune).  host_out (may be null): the result's host arrays
+    struct Part {
+        const Program *program;
+        float rotation[3][3];
+        float scale;
+        float translation[3];
+        int op = SDFHIP_COMBINE_UNION;
+    };
+    void Compose(const std::vector<Part> &parts, int depth = -1, sdfhip_compose_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
+    {
+        std::vector<sdfhip_instance> list(parts.size());
+        for (size_t k = 0; k < parts.size(); k++) {
+            if (!parts[k].program || !parts[k].program->scene) throw Error(SDFHIP_ERR_ARG, "Compose: a part has no model loaded");
+            sdfhip_instance &in = list[k];
+            in.scene = parts[k].program->scene;
+            in.op = parts[k].op;
+            for (int i = 0; i < 3; i++) {
+                for (int j = 0; j < 3; j++) in.rotation[i][j] = parts[k].rotation[i][j];
+                in.translation[i] = parts[k].translation[i];
+            }
+            in.scale = parts[k].scale;
+        }
+        const sdfhip_compose_options opt = { (uint32_t)sizeof(sdfhip_compose_options), depth };
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_compose(list.data(), (uint32_t)list.size(), &opt, &fresh, host_out, stats));
+        if (scene) sdfhip_scene_free(scene);
+        scene = fresh;
+    }
     // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
     // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at
     // index (k * ny + j) * nx + i and at origin + (i, j, k) * spacing in the unit cube's coordinates, stored value * value_scale =

@@ -5,15 +5,15 @@ mirror of the reference's interface for that path: OctData (.asdf), Logic
 (camera -> Info), Scene.Draw (Program.Draw's compute pass).
 """
 from . import _lib, tiles
-from ._lib import (VOLUME_F16, VOLUME_F32, Volume, VolumeStats, BRUSH_BOX, BRUSH_SPHERE, COMBINE_INTERSECT, COMBINE_SUBTRACT, COMBINE_UNION, CombineOptions, CombineStats, EDIT_ADD, EDIT_CARVE, FLAG_COMPACT, FLAG_COUNT, FLAG_DISPLAY, FLAG_DISPLAY_DEBUG, FLAG_TILE_ORDER, FLAG_WIRE, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_STACK, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_HIT, QUERY_INVALID, TUNE_ONE_KERNEL, TUNE_SHADOW_QUEUE, Edit, EditStats, PruneOptions, PruneStats, Placement, PlaceStats, OFFSET_GROW, OFFSET_SHELL, Clearance, OffsetOptions, OffsetStats, BLEND_UNION, BLEND_INTERSECT, BLEND_SUBTRACT, BLEND_MORPH, BlendOptions, BlendStats,
+from ._lib import (VOLUME_F16, VOLUME_F32, Volume, VolumeStats, BRUSH_BOX, BRUSH_SPHERE, COMBINE_INTERSECT, COMBINE_SUBTRACT, COMBINE_UNION, CombineOptions, CombineStats, EDIT_ADD, EDIT_CARVE, FLAG_COMPACT, FLAG_COUNT, FLAG_DISPLAY, FLAG_DISPLAY_DEBUG, FLAG_TILE_ORDER, FLAG_WIRE, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_STACK, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_HIT, QUERY_INVALID, TUNE_ONE_KERNEL, TUNE_SHADOW_QUEUE, Edit, EditStats, PruneOptions, PruneStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, OFFSET_GROW, OFFSET_SHELL, Clearance, OffsetOptions, OffsetStats, BLEND_UNION, BLEND_INTERSECT, BLEND_SUBTRACT, BLEND_MORPH, BlendOptions, BlendStats,
                    Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiStats, TriMeshOptions, TriMeshStats, PathTrace, Probe, Ray, SdfHipError, Stats)
 from .logic import Logic
 from .octdata import OctData, dragon_standin, knot_point_cloud, sphere_d4, torus_d6, write_ply
-from .renderer import HostFrame, LoadMeshObj, LoadMeshPly, MultiScene, SaveMeshObj, SaveMeshPly, Scene, TriMesh, lattice_of_depth, placement, placement_fit, device_bandwidth, device_count, device_pci_bus_id, sdfgen_trim, unorm_table
+from .renderer import HostFrame, LoadMeshObj, LoadMeshPly, MultiScene, SaveMeshObj, SaveMeshPly, Scene, TriMesh, lattice_of_depth, placement, placement_fit, linear_array, circular_array, device_bandwidth, device_count, device_pci_bus_id, sdfgen_trim, unorm_table
 
 __all__ = [
     "BRUSH_BOX", "BRUSH_SPHERE", "EDIT_ADD", "EDIT_CARVE", "Edit", "EditStats", "PruneOptions", "PruneStats",
-    "COMBINE_UNION", "COMBINE_INTERSECT", "COMBINE_SUBTRACT", "CombineOptions", "CombineStats", "Placement", "PlaceStats", "placement", "placement_fit", "VOLUME_F32", "VOLUME_F16", "Volume", "VolumeStats", "lattice_of_depth", "Measure", "MeasureOptions",
+    "COMBINE_UNION", "COMBINE_INTERSECT", "COMBINE_SUBTRACT", "CombineOptions", "CombineStats", "Placement", "PlaceStats", "placement", "placement_fit", "Instance", "ComposeOptions", "ComposeStats", "linear_array", "circular_array", "VOLUME_F32", "VOLUME_F16", "Volume", "VolumeStats", "lattice_of_depth", "Measure", "MeasureOptions",
     "OFFSET_GROW", "OFFSET_SHELL", "Clearance", "OffsetOptions", "OffsetStats",
     "BLEND_UNION", "BLEND_INTERSECT", "BLEND_SUBTRACT", "BLEND_MORPH", "BlendOptions", "BlendStats",
     "QUERY_HIT", "QUERY_ESCAPED", "QUERY_EXHAUSTED", "QUERY_INVALID", "Probe", "Ray", "Hit",

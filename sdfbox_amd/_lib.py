@@ -54,7 +54,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -218,6 +218,41 @@ else:
 
 
     assert (ctypes.sizeof(Placement), ctypes.sizeof(PlaceStats)) == (60, 40)
+
+
+    class Instance(ctypes.Structure):
+        """sdfhip_instance: one placed instance of a resident scene for sdfhip_scene_compose.  scene: the handle (a c_void_p or its
+        value); op: COMBINE_UNION / _INTERSECT / _SUBTRACT, how the instance joins what precedes it; rotation, scale, translation:
+        as Placement's."""
+        _fields_ = [("scene", ctypes.c_void_p), ("op", ctypes.c_int32), ("rotation", (ctypes.c_float * 3) * 3), ("scale", ctypes.c_float),
+                    ("translation", ctypes.c_float * 3)]
+
+        def __init__(self, scene=None, op=0, rotation=((1, 0, 0), (0, 1, 0), (0, 0, 1)), scale=1.0, translation=(0, 0, 0)):
+            rows = [[float(x) for x in row] for row in rotation]
+            if len(rows) != 3 or any(len(row) != 3 for row in rows):
+                raise ValueError("rotation must be 3 x 3")
+            t = [float(x) for x in translation]
+            if len(t) != 3:
+                raise ValueError("translation must have three components")
+            super().__init__(getattr(scene, "value", scene), int(op), ((ctypes.c_float * 3) * 3)(*[(ctypes.c_float * 3)(*row) for row in rows]),
+                             float(scale), (ctypes.c_float * 3)(*t))
+
+
+    class ComposeOptions(ctypes.Structure):
+        """sdfhip_compose_options: depth None = the largest depth among the sources, else 0..12."""
+        _fields_ = [("size", ctypes.c_uint32), ("depth", ctypes.c_int32)]
+
+        def __init__(self, depth=None):
+            super().__init__(ctypes.sizeof(type(self)), -1 if depth is None else int(depth))
+
+
+    class ComposeStats(ctypes.Structure):
+        _fields_ = [("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("instances", ctypes.c_uint32),
+                    ("samples", ctypes.c_uint64), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
+                    ("pad_", ctypes.c_uint32)]
+
+
+    assert (ctypes.sizeof(Instance), ctypes.sizeof(ComposeOptions), ctypes.sizeof(ComposeStats)) == (64, 8, 40)
 
 
     class Volume(ctypes.Structure):
@@ -464,6 +499,7 @@ _SIG = {
     "sdfhip_scene_prune": (_c.c_int, [_vp, _c.POINTER(PruneOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PruneStats)]),
     "sdfhip_scene_combine": (_c.c_int, [_vp, _vp, _c.c_int32, _c.POINTER(CombineOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(CombineStats)]),
     "sdfhip_scene_place": (_c.c_int, [_vp, _c.POINTER(Placement), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(PlaceStats)]),
+    "sdfhip_scene_compose": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(ComposeOptions), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(ComposeStats)]),
     "sdfhip_volume_build": (_c.c_int, [_c.c_int, _vp, _c.POINTER(Volume), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(VolumeStats)]),
     "sdfhip_volume_build_device": (_c.c_int, [_c.c_int, _vp, _c.POINTER(Volume), _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(VolumeStats)]),
     "sdfhip_scene_volume": (_c.c_int, [_vp, _c.POINTER(Volume), _vp]),

@@ -9,6 +9,7 @@
 #include "host_support.h"
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <type_traits>
 
@@ -55,6 +56,29 @@ inline Source read_source(sdfhip_scene *s)
 {
     std::lock_guard<std::mutex> lk(s->lock);
     return Source{scene_of(s), form_of(s), s->depth, s->device, s->stack_ok};
+}
+
+// What sdfhip_scene_place and sdfhip_scene_compose refuse of a similarity p = s R x + t, before any device call: a non-finite field,
+// s <= 0, a rotation with max |(R R^T - I)_ij| > 1e-4 (in double; the bound defines the interface, mirrors pass).  what: the
+// message's prefix -- the entry point's name, and for an instance its index.
+inline int check_similarity(const char *what, const float (*rotation)[3], float scale, const float *translation)
+{
+    bool finite = std::isfinite(scale);
+    for (int i = 0; i < 3; i++) {
+        finite = finite && std::isfinite(translation[i]);
+        for (int j = 0; j < 3; j++) finite = finite && std::isfinite(rotation[i][j]);
+    }
+    if (!finite) return fail(SDFHIP_ERR_ARG, "%s: rotation, scale and translation must be finite", what);
+    if (!(scale > 0.0f)) return fail(SDFHIP_ERR_ARG, "%s: scale %g is not above 0", what, (double)scale);
+    double worst = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            double dot = 0.0;
+            for (int k = 0; k < 3; k++) dot += (double)rotation[i][k] * (double)rotation[j][k];
+            worst = std::max(worst, std::fabs(dot - (i == j ? 1.0 : 0.0)));
+        }
+    if (worst > 1e-4) return fail(SDFHIP_ERR_ARG, "%s: the rotation is not orthogonal (max |R R^T - I| = %g, the bound 1e-4)", what, worst);
+    return SDFHIP_OK;
 }
 
 struct LevelBuild {

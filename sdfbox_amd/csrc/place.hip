@@ -38,21 +38,7 @@ namespace {
 int check_placement(const sdfhip_placement *pl)
 {
     if (const int rc = check_options_size("scene_place", pl, sizeof(sdfhip_placement), "size = sizeof(sdfhip_placement)")) return rc;
-    bool finite = std::isfinite(pl->scale);
-    for (int i = 0; i < 3; i++) {
-        finite = finite && std::isfinite(pl->translation[i]);
-        for (int j = 0; j < 3; j++) finite = finite && std::isfinite(pl->rotation[i][j]);
-    }
-    if (!finite) return fail(SDFHIP_ERR_ARG, "scene_place: rotation, scale and translation must be finite");
-    if (!(pl->scale > 0.0f)) return fail(SDFHIP_ERR_ARG, "scene_place: scale %g is not above 0", (double)pl->scale);
-    double worst = 0.0;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double dot = 0.0;
-            for (int k = 0; k < 3; k++) dot += (double)pl->rotation[i][k] * (double)pl->rotation[j][k];
-            worst = std::max(worst, std::fabs(dot - (i == j ? 1.0 : 0.0)));
-        }
-    if (worst > 1e-4) return fail(SDFHIP_ERR_ARG, "scene_place: the rotation is not orthogonal (max |R R^T - I| = %g, the bound 1e-4)", worst);
+    if (const int rc = check_similarity("scene_place", pl->rotation, pl->scale, pl->translation)) return rc;
     if (pl->depth < -1 || pl->depth > TREE_MAX_DEPTH)
         return fail(SDFHIP_ERR_ARG, "scene_place: depth %d is neither -1 nor 0..%d", pl->depth, TREE_MAX_DEPTH);
     return SDFHIP_OK;

@@ -94,6 +94,49 @@ def placement_fit(measure, yaw=0, pitch=0, roll=0, size=0.8, to=(0.5, 0.5, 0.5))
     return placement(yaw, pitch, roll, float(size) / side, about=(lo + hi) * 0.5, to=to)
 
 
+def linear_array(placement, step, count):
+    """`count` placements (R, s, t) for Scene.Compose in a row: copy i is `placement` = (R, s, t) translated by i * step.  Computed
+    in double from the arguments and rounded to float32 once, at the end; copy 0 is the input."""
+    R, s, t = placement
+    count = int(count)
+    if count < 1:
+        raise ValueError("linear_array: count must be at least 1")
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    step = np.asarray(step, dtype=np.float64).reshape(3)
+    return [(R.astype(np.float32), np.float32(float(s)), (t + float(i) * step).astype(np.float32)) for i in range(count)]
+
+
+def _axis_rotation(axis, angle):
+    """the rotation by `angle` (radians, right-handed) about the unit vector `axis`, in double (Rodrigues); the identity exactly at 0"""
+    K = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]])
+    return np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+
+
+def circular_array(placement, centre, axis, count):
+    """`count` placements (R, s, t) for Scene.Compose round a circle: copy i is `placement` = (R, s, t) turned by 360 * i / count
+    degrees (right-handed) about the line through `centre` along the unit vector `axis`: with Q that rotation, (Q R, s, Q t +
+    (centre - Q centre)).  Q is a proper rotation, so a mirror stays a mirror.  Computed in double from the arguments and rounded to
+    float32 once, at the end; copy 0 is the input.  Raises ValueError on an axis that is not of length 1 (to 1e-6)."""
+    R, s, t = placement
+    count = int(count)
+    if count < 1:
+        raise ValueError("circular_array: count must be at least 1")
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    a = np.asarray(axis, dtype=np.float64).reshape(3)
+    length = float(np.sqrt((a * a).sum()))
+    if not abs(length - 1.0) <= 1e-6:
+        raise ValueError("circular_array: the axis must be a unit vector")
+    a = a / length
+    out = []
+    for i in range(count):
+        Q = _axis_rotation(a, 2.0 * np.pi * i / count)
+        out.append(((Q @ R).astype(np.float32), np.float32(float(s)), (Q @ t + (c - Q @ c)).astype(np.float32)))
+    return out
+
+
 def lattice_of_depth(d):
     """(shape, origin, spacing) for Scene.Volume / Scene.FromVolume: the lattice whose vertices are every corner and every inner
     centre of a tree of depth d -- 2^d + 1 samples along each axis, from the origin, 2^-d apart (every point a build to depth d
@@ -237,6 +280,51 @@ class Scene:
         raw = _lib.COctData()
         st = _lib.PlaceStats()
         check(lib.sdfhip_scene_place(self._h, ctypes.byref(pl), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        res._describe()
+        out = [res]
+        if want_octdata:
+            out.append(OctData._from_native(raw))
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    @staticmethod
+    def Compose(parts, depth=None, want_octdata=False, want_stats=False):
+        """Composition (sdfhip_scene_compose): ONE new Scene from many placed instances, in a single pass.  parts: a list of
+        (scene, (R, s, t)) or (scene, (R, s, t), op) -- a Scene, its placement as Place takes it, and how the instance joins what
+        precedes it in the list: COMBINE_UNION (the default), COMBINE_INTERSECT or COMBINE_SUBTRACT; the first is a union.  The same
+        Scene may appear in as many parts as wanted (linear_array() and circular_array() make the placements of a pattern).  Every
+        instance's own field is evaluated at every point of the result's lattice, folded in float in list order and rounded to a byte
+        once: one instance is Place byte for byte, and the result is NOT Combine of Places (one quantisation, not two).  depth: None =
+        the largest depth among the parts' scenes, else 0..12.  Nothing is pruned (chain Prune); every source is left as it was.
+        Returns what Place returns; want_stats: a ComposeStats.  Raises ValueError on an empty list and on a part that is not such a
+        tuple."""
+        from .octdata import OctData
+        parts = list(parts)
+        if not parts:
+            raise ValueError("Compose: no parts")
+        items = []
+        for k, part in enumerate(parts):
+            if not isinstance(part, (tuple, list)) or len(part) not in (2, 3):
+                raise ValueError(f"Compose: part {k} is neither (scene, (R, s, t)) nor (scene, (R, s, t), op)")
+            scene, pl = part[0], part[1]
+            if not isinstance(scene, Scene):
+                raise ValueError(f"Compose: part {k}: not a Scene")
+            if not isinstance(pl, (tuple, list)) or len(pl) != 3:
+                raise ValueError(f"Compose: part {k}: the placement is not (R, s, t)")
+            R, sc, t = pl
+            op = _lib.COMBINE_UNION if len(part) == 2 else int(part[2])
+            items.append(_lib.Instance(scene._h, op, np.asarray(R, dtype=np.float32).reshape(3, 3).tolist(), sc,
+                                       np.asarray(t, dtype=np.float32).reshape(3).tolist()))
+        arr = (_lib.Instance * len(items))(*items)
+        opt = _lib.ComposeOptions(depth)
+        res = Scene.__new__(Scene)
+        res._h = ctypes.c_void_p()
+        res.device = parts[0][0].device
+        raw = _lib.COctData()
+        st = _lib.ComposeStats()
+        check(lib.sdfhip_scene_compose(arr, len(items), ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None,
+                                       ctypes.byref(st)))
         res._describe()
         out = [res]
         if want_octdata:
