@@ -50,21 +50,22 @@ def value(instances, p):
     return v
 
 
-def node_values(instances, coords, depth):
+def node_values(instances, coords, depth, value_of=value):
     """corner values (n, 8) and centre values (n,) of the nodes with integer coordinates coords (n, 3) at `depth`"""
     S = f32(2.0 ** -depth)
     coords = np.asarray(coords, dtype=np.int64).reshape(-1, 3)
     pts = np.concatenate([(2 * (coords[:, None, :] + CORNER[None])).reshape(-1, 3), 2 * coords + 1])     # in units of S / 2
     uniq, inv = np.unique(pts, axis=0, return_inverse=True)
-    v = value(instances, uniq.astype(f32) * f32(S * f32(0.5)))[inv.reshape(-1)]
+    v = value_of(instances, uniq.astype(f32) * f32(S * f32(0.5)))[inv.reshape(-1)]
     n = len(coords)
     return v[:8 * n].reshape(n, 8), v[8 * n:]
 
 
-def compose(parts, depth=-1, want_counts=False):
+def compose(parts, depth=-1, want_counts=False, value_of=value):
     """parts: see as_instances -> (structs, values) of the composed tree (new arrays), breadth first.  depth: -1 = the largest depth
     among the instances' sources, else 0..12.  want_counts: also {"depth_out", "levels", "samples"}; samples = instances * (9 for the
-    root + 35 for every block of eight siblings), the look-ups the header counts."""
+    root + 35 for every block of eight siblings), the look-ups the header counts.  value_of: another route to value(instances, p),
+    for a list too long to evaluate instance by instance (compose_cases.folded_value, which tests/test_compose.py holds to value)."""
     instances = as_instances(parts)
     max_depth = max(tree_depth(src[0]) for src, _, _ in instances) if depth < 0 else int(depth)
     coords = np.zeros((1, 3), dtype=np.int64)
@@ -75,7 +76,7 @@ def compose(parts, depth=-1, want_counts=False):
         S = f32(2.0 ** -d)
         n = len(coords)
         points += 9 if d == 0 else 35 * (n // 8)
-        cv, mv = node_values(instances, coords, d)
+        cv, mv = node_values(instances, coords, d, value_of)
         V_out.append(from_float(cv, S))
         links = np.full((n, 2), -1, dtype=np.int32)
         links[:, 0] = parent

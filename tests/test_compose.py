@@ -214,6 +214,64 @@ def test_structure(sb, name):
         assert len(S_) > 1000 and counts["depth_out"] == (6 if depth < 0 else depth)
 
 
+# ---- depth 12 in the far corner, and the instance limit -------------------------------------------------------------------------------
+def test_the_far_corner_is_12_levels_deep_with_coordinates_above_2_to_the_10():
+    import volume_cases as vc
+    S_, V_, counts = cc.restated("corner_d12")
+    parts, depth = cc.case("corner_d12")
+    assert depth == 12 and len(parts) == 2 and {src for src, _, _ in parts} == {"sphere_d4"}
+    assert all(float(pl[1]) == 2.0 ** -7 for _, pl, _ in parts) and np.array_equal(parts[1][1][0], plr.IDENTITY)
+    assert counts["depth_out"] == 12 and len(S_) == cc.CORNER_D12_NODES == 63233 <= 400_000
+    sizes = vc.level_sizes(S_)
+    assert len(sizes) == 13 and sizes[12] == 48120 > 32768, "the last level is past one chunk of the shared scan"
+    blocks = vc.last_blocks(S_)
+    assert (blocks > 2 ** 10).all(1).any() and blocks.max() < 2 ** 11
+    # the second instance sits on the face y = 1 where x and z are small: a packed word with a large y beside a small x
+    assert ((blocks[:, 1] > 2 ** 10) & (blocks[:, 0] < 2 ** 5) & (blocks[:, 2] < 2 ** 5)).any()
+    # one instance: the placement's restatement, array for array, in the same corner
+    one, want = cc.restated("corner_d12_one"), plr.place(tree("sphere_d4"), *parts[0][1], 12, want_counts=True)
+    assert same(one, want) and one[2] == want[2] and len(one[0]) == cc.CORNER_D12_ONE_NODES == 33577
+    assert (vc.last_blocks(one[0]) > 2 ** 10).all(1).any()
+
+
+def test_the_fold_over_distinct_pairs_is_the_restatement_on_the_first_130():
+    # the 4096-long list is restated by evaluating its 16 distinct (source, placement) pairs once and folding in list order: held
+    # here to compose_restatement.compose itself, instance by instance, on the list's first 130 entries -- past two waves of 64
+    parts, depth = cc.case("limit_130")
+    assert [(src, op) for src, _, op in parts] == [(src, op) for src, _, op in cc.case(f"limit_{cc.LIMIT}")[0][:130]]
+    want = cr.compose(cc.with_trees(parts), depth, want_counts=True)
+    got = cc.restated("limit_130")
+    assert same(got, want) and got[2] == want[2] and len(got[0]) == cc.LIMIT_NODES[130]
+    # ... and point by point on scattered points, all three ops among the 130
+    p = np.random.default_rng(5).random((500, 3)).astype(np.float32)
+    inst = cr.as_instances(cc.with_trees(parts))
+    assert {op for _, _, op in inst} == {U, I, S}
+    assert np.array_equal(cc.folded_value(inst, p).view(np.uint32), cr.value(inst, p).view(np.uint32))
+
+
+def test_the_long_lists_are_what_they_are_for():
+    full, depth = cc.case(f"limit_{cc.LIMIT}")
+    assert len(full) == 4096 and depth in (3, 4) and full[0][2] == U
+    pairs = cc.limit_pairs()
+    assert len(pairs) == 16 and {src for src, _ in pairs} == {"leaf", "nine", "blocks_65"}
+    assert len({(src, pl[0].tobytes(), pl[1].tobytes(), pl[2].tobytes()) for src, pl in pairs}) == 16
+    assert all(full[k][0] == pairs[k % 16][0] and np.array_equal(full[k][1][2], pairs[k % 16][1][2]) for k in range(4096))
+    # the ops vary with k: no pair meets the same op every time, and the list is not periodic in 16
+    ops = np.array([op for _, _, op in full])
+    assert {int(o) for o in ops} == {U, I, S} and not np.array_equal(ops[16:32], ops[32:48])
+    assert all(len(set(ops[j::16].tolist())) >= 2 for j in range(16))
+    for n in (63, 64, cc.LIMIT):
+        assert len(cc.case(f"limit_{n}")[0]) == n
+        S_, V_, counts = cc.restated(f"limit_{n}")
+        assert len(S_) == cc.LIMIT_NODES[n] and counts["depth_out"] == depth, n
+        assert counts["samples"] == n * (9 + 35 * ((len(S_) - 1) // 8)), n
+    # later repeats still change the tree: without its last 16 entries, and without its second half, the list gives another tree
+    whole = cc.restated(f"limit_{cc.LIMIT}")
+    for n in (4080, 2048):
+        part = cc.restated(f"limit_{n}")
+        assert not (len(part[0]) == len(whole[0]) and np.array_equal(part[1], whole[1])), n
+
+
 # ---- the array helpers --------------------------------------------------------------------------------------------------------------
 def test_linear_array(sb):
     base = sb.placement(30, 20, -70, 0.37, about=(0.2, 0.6, 0.5), to=(0.2, 0.3, 0.4))

@@ -1,7 +1,9 @@
 """Composition on the GPU (sdfhip_scene_compose), both flavours of the library: the composed tree is the CPU restatement's
 (tests/compose_restatement.py) byte for byte -- every case of tests/compose_cases.py -- its statistics are the restatement's counts,
 instances of every cursor form in one call give the same bytes, its frames are the oracle's on the restated arrays, the sources are
-untouched, a composition chains with the prune and the combination as the restatements do, and the errors are status codes."""
+untouched, a composition chains with the prune and the combination as the restatements do, and the errors are status codes.  The
+second round's cases: depth 12 in the far corner (that its one-instance variant is the placement's tree is tests/test_compose.py's, on
+the restatements) and lists of 63, 64 and 4096 instances.  Zoo trees as sources: tests/test_gpu_zoo_volumes.py."""
 import ctypes
 import json
 import os
@@ -18,8 +20,9 @@ import edit_restatement as er
 import place_restatement as plr
 import prune_restatement as pr
 from conftest import REPO, assert_frames_identical, make_camera
-from test_gpu_combine import tree
 from test_gpu_prune import assert_same_tree
+
+tree = cc.tree
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +121,9 @@ def test_the_cases_are_what_they_are_for():
     assert any(b > 4 and b % 4 for b in blocks), blocks
     # arrays that had to grow: they start at 1.5 times the distinct sources together
     assert FAR_NODES > 2 * ((len(tree("torus_d6")[0]) + len(tree("sphere_d4")[0])) * 3 // 2)
+    # depth 12 in the far corner and the instance limit: tests/test_compose.py pins them without a GPU; here what the GPU run leans on
+    assert cc.restated("corner_d12")[2]["depth_out"] == 12 and len(cc.restated("corner_d12")[0]) == cc.CORNER_D12_NODES
+    assert [len(cc.case(f"limit_{n}")[0]) for n in (63, 64, cc.LIMIT)] == [63, 64, 4096] and cc.LIMIT == 4096
 
 
 def test_instances_of_every_cursor_form_in_one_call(sb):

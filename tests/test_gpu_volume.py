@@ -2,7 +2,10 @@
 built tree is the CPU restatement's (tests/volume_restatement.py) byte for byte -- every grid of tests/volume_cases.py, through the
 host entry and from a torch tensor -- its statistics are the restatement's counts; a scene read on a lattice is what the sampler
 answers at the same points, bit for bit, with every cursor form; the two directions compose into the placement's identity; the
-result renders, prunes, combines and measures as any other scene; and the errors are status codes."""
+result renders, prunes, combines and measures as any other scene; and the errors are status codes.  The second round (the cases of
+volume_cases.py from corner_d12 on): depth 12 in the far corner, grids on the negative side and of the other sign, the edges of
+float16 in both directions, and more samples than k_volume_check strides with.  Zoo trees as sources, and the lattice past
+k_volume_out's stride: tests/test_gpu_zoo_volumes.py."""
 import ctypes
 import json
 import os
@@ -23,11 +26,11 @@ from test_gpu_prune import assert_same_tree
 
 pytestmark = pytest.mark.gpu
 
-DEVICE_ENTRY = ("sphere17_d4", "aniso_inset_d5", "torus33_f16_d6")        # also built from a torch tensor
+DEVICE_ENTRY = ("sphere17_d4", "aniso_inset_d5", "torus33_f16_d6", "corner_d12", "corner_d12_f16", "negative_scale_d4",
+                "half_edges_scaled_d3")                                   # also built from a torch tensor
 OUT_SOURCES = ["leaf", "nine", "sphere_d4", "torus_edited", "off_d7"]
 # (shape (nz, ny, nx), origin, spacing): a 5 x 1 x 7 lattice that sticks out of the cube on every side, and one element
-STICKS_OUT = ((7, 1, 5), (-0.3, 0.4, -0.45), 0.31)
-ONE = ((1, 1, 1), (0.3, 0.6, 0.45), 1.0)
+STICKS_OUT, ONE = vc.STICKS_OUT, vc.ONE
 
 
 @pytest.fixture(scope="module", params=["product", "lab"])
@@ -206,6 +209,60 @@ def test_non_finite_samples_and_bad_arguments_are_status_codes(sb):
         assert L.lib.sdfhip_scene_volume(scene._h, ctypes.byref(sb.Volume((2, 2, 2), (0, 0, 0), 1.0, 0.0, 0, 3)), out.ctypes.data) == L.ERR_ARG
         assert L.lib.sdfhip_scene_volume(scene._h, ctypes.byref(sb.Volume((2, 2, 2), (0, 0, 0), 1.0)), out.ctypes.data) == L.OK
         assert np.array_equal(out.reshape(2, 2, 2), scene.Volume((2, 2, 2)))
+
+
+def test_non_finite_samples_past_the_first_stride_are_counted(sb):
+    # 81^3 = 531 441 samples against the 524 288 threads k_volume_check strides with: the last 7 153 are a thread's second trip.  One
+    # bad sample alone at the first and the last index of either trip; then every 97th sample, NaN and both infinities in turn -- a
+    # count that every lane, wave and workgroup contributes to.  The message's count is exactly what was planted
+    import torch
+    c = vc.case("sphere81_d4")
+    total, stride = c["grid"].size, 2048 * 256
+    assert total == 531441 > stride
+    every = np.arange(0, total, 97)
+    assert len(every) == 5479 and every[-1] > stride
+    plantings = [(np.array([i]), [np.nan]) for i in (0, stride - 1, stride, total - 1)] + [(every, [np.nan, np.inf, -np.inf])]
+    for dtype in (np.float32, np.float16):
+        clean = c["grid"].astype(dtype)
+        for at, bad in plantings:
+            grid = clean.copy()
+            grid.reshape(-1)[at] = np.resize(np.array(bad, dtype=dtype), len(at))
+            assert int((~np.isfinite(grid)).sum()) == len(at)
+            for g in (grid, torch.from_numpy(grid).cuda()):
+                with pytest.raises(sb.SdfHipError) as e:
+                    sb.Scene.FromVolume(g, c["origin"], c["spacing"], c["depth"])
+                assert e.value.code == sb._lib.ERR_ARG, (dtype, at[:3])
+                assert f" {len(at)} of the grid's {total} samples are not finite" in str(e.value), (dtype, at[:3], str(e.value))
+    # the clean grid builds afterwards to the restatement's tree, from the host and from the device
+    check_build(sb, "sphere81_d4")
+    check_build(sb, "sphere81_d4", torch.from_numpy(c["grid"].copy()).cuda())
+
+
+def test_half_precision_out_beyond_its_precision_and_below_its_normals(sb):
+    # far outside the cube: elements 0.013 apart at distance 300, where a half's ulp is 0.25 -- neighbours differ in float32 and round
+    # to the same half, some of them across a tie's neighbourhood; nothing overflows (the header leaves an overflow undefined)
+    far = ((2, 3, 40), (-300.0, 0.3, 0.4), 0.013)
+    bits = lambda a: a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
+    with upload(sb, "torus_edited") as scene:
+        want = restated_out("torus_edited", far)
+        half = restated_out("torus_edited", far, np.float16)
+        assert np.abs(want).max() < 65504 and np.isfinite(half).all()
+        assert len(np.unique(bits(want))) > 4 * len(np.unique(bits(half))) > 4
+        assert np.array_equal(bits(scene.Volume(*far)), bits(want))
+        assert np.array_equal(bits(scene.Volume(*far, dtype=np.float16)), bits(half))
+    # near the surface of the depth-12 sphere after a prune that removes nothing it should not: distances of a few 2^-12 / 255, which
+    # round to subnormal halves (below 2^-14)
+    S, V, _ = vc.restated("corner_d12")
+    PS, PV = pr.prune(S, V, 0)
+    centre, r = np.array(vc.CORNER_D12[:3]), vc.CORNER_D12[3]
+    near = ((9, 9, 9), tuple(float(x) for x in np.floor((centre + r / np.sqrt(3.0)) * 4096) / 4096 - 4 * 2.0 ** -12), 2.0 ** -12)
+    want = vr.volume_out((PS, PV), *near, dtype=np.float16)
+    subnormal = (bits(want) & 0x7C00 == 0) & (bits(want) & 0x03FF != 0)
+    assert subnormal.sum() > 20 and (want[subnormal] < 0).any() and (want[subnormal] > 0).any()
+    with build(sb, "corner_d12") as scene, scene.Prune(0) as pruned:
+        assert pruned.Length == len(PS) <= len(S)
+        assert np.array_equal(bits(pruned.Volume(*near, dtype=np.float16)), bits(want))
+        assert np.array_equal(bits(pruned.Volume(*near)), bits(vr.volume_out((PS, PV), *near)))
 
 
 def test_an_allocation_that_fails_is_nomem_and_leaves_the_library_working():

@@ -119,6 +119,55 @@ def test_the_cases_are_what_they_are_for():
     assert vc.case("torus33_f16_d6")["grid"].dtype == np.float16
 
 
+def test_the_second_rounds_cases_are_what_they_are_for():
+    # depth 12 in the far corner: 12 levels, and blocks of the last level with all three coordinates above 2^10 -- bit 10 of the
+    # packed y and of x set, the emit's doubling past 2^11
+    for name in ("corner_d12", "corner_d12_f16"):
+        S, _, counts = vc.restated(name)
+        assert counts["depth_out"] == 12 and len(S) == vc.NODES[name] == 12433, name
+        assert vc.level_sizes(S) == [1, 8, 32, 32, 32, 32, 56, 64, 160, 336, 936, 2488, 8256], name
+        blocks = vc.last_blocks(S)
+        assert len(blocks) == 8256 // 8 and (blocks > 2 ** 10).all(1).any() and blocks.max() < 2 ** 11, name
+    c = vc.case("corner_d12")
+    assert c["grid"].shape == (17, 17, 17) and c["spacing"] == 2.0 ** -11 and c["origin"][0] + 16 * c["spacing"] < 1
+    assert vc.case("corner_d12_f16")["grid"].dtype == np.float16
+    assert not np.array_equal(vc.restated("corner_d12")[1], vc.restated("corner_d12_f16")[1]), "the rounding to half moves bytes"
+    # the cube strictly inside the grid's box, off its lattice
+    c = vc.case("wraps_d5")
+    nz, ny, nx = c["grid"].shape
+    assert (nx, ny, nz) == (36, 37, 33) and max(c["origin"]) < 0 and all(o + (n - 1) * c["spacing"] > 1 for o, n in zip(c["origin"], (nx, ny, nz)))
+    assert all((0 - o) / c["spacing"] % 1 > 0.01 for o in c["origin"])
+    assert len(vc.restated("wraps_d5")[0]) == len(vc.restated("voxel_units_d5")[0]) == 13385
+    # the middle of the cube along x, out of it on the negative side along y, with the surface inside the grid's box there
+    c, was = vc.case("inset_negative_d5"), vc.case("aniso_inset_d5")
+    assert c["grid"].shape == was["grid"].shape and c["spacing"] == was["spacing"]
+    assert 0.25 < c["origin"][0] and c["origin"][0] + 8 * c["spacing"] < 0.75 and c["origin"][1] < -0.1 < 0.25 < c["origin"][1] + 12 * c["spacing"] < 1
+    assert (c["grid"][:, :5, :] > 0).all() and (c["grid"] < 0).any(), "five planes lie below y = 0, outside the solid; the surface crosses the box"
+    assert len(vc.restated("inset_negative_d5")[0]) == 4809
+    # a negative scale: the negated grid's tree is sphere17_d4's, array for array
+    c = vc.case("negative_scale_d4")
+    assert c["value_scale"] == -1.0 and np.array_equal(c["grid"], -vc.case("sphere17_d4")["grid"])
+    for a, b in zip(vc.restated("negative_scale_d4")[:2], vc.restated("sphere17_d4")[:2]):
+        assert np.array_equal(a, b)
+    # more samples than k_volume_check's 2048 workgroups of 256 threads; the same tree as the 17^3 grid's
+    c = vc.case("sphere81_d4")
+    assert c["grid"].size == 531441 > 2048 * 256
+    for a, b in zip(vc.restated("sphere81_d4")[:2], vc.restated("sphere17_d4")[:2]):
+        assert np.array_equal(a, b)
+    # the edges of float16 are among the samples, the large ones do not overflow under either scale, and they move bytes
+    edges = np.array(vc.HALF_EDGES, dtype=np.float16).view(np.uint16)
+    assert sorted(edges.tolist()) == [0x0001, 0x0300, 0x0400, 0x7BFF, 0x8000, 0x8001, 0x8400, 0xFBFF]
+    for name, scale in (("half_edges_d3", 1.0), ("half_edges_scaled_d3", 2.0 ** -16)):
+        c = vc.case(name)
+        bits = c["grid"].reshape(-1).view(np.uint16)
+        assert c["grid"].dtype == np.float16 and c["grid"].shape == (9, 9, 9) and c["value_scale"] == scale, name
+        assert all(int((bits == e).sum()) >= 3 for e in edges), name
+        assert np.isfinite(c["grid"]).all() and len(vc.restated(name)[0]) == 585, name
+        plain = vc._case(vc.sphere, (9, 9, 9), (0, 0, 0), 1.0 / 8, 3, dtype=np.float16, stored=1.0 / scale)
+        assert (vr.build(plain["grid"], plain["origin"], plain["spacing"], 3, scale)[1] != vc.restated(name)[1]).sum() > 100, name
+    assert np.abs(vc.case("half_edges_scaled_d3")["grid"].astype(np.float64)).max() == 65504.0
+
+
 def test_a_truncated_field_splits_every_node_below_its_truncation():
     # include/sdfhip.h says so: the split rule assumes a distance.  |value| <= tau = 1/16 everywhere, so fabsf(value(centre)) < 2 S
     # holds for every node of depths 0..4 (2 S >= 1/8 > tau): levels up to 5 are full

@@ -1,10 +1,23 @@
 """Trees built to break a consumer, shared by the tests of the renderer, the queries, the mesh, the edit, the prune, the combination,
-the placement and the measure.  A plain helper module
+the placement, the measure, the volume read-out and the composition.  A plain helper module
 (like the *_restatement.py files): generators of consistent trees that no builder would lay out -- depth-first order, a chain along
 one corner, blocks appended under randomly chosen leaves, node counts one past a kernel's chunk, row and wave -- byte fillers that are
 no distance field, the named trees `zoo()` every zoo test uses, the edit cases of tests/test_tree_zoo.py and
-tests/test_gpu_tree_zoo.py and the prune, combine, place and measure cases of tests/test_zoo_builders.py and
-tests/test_gpu_zoo_builders.py, with a cache of their restated results.
+tests/test_gpu_tree_zoo.py, the prune, combine, place and measure cases of tests/test_zoo_builders.py and
+tests/test_gpu_zoo_builders.py, and the volume-out and compose cases of tests/test_zoo_volumes.py and tests/test_gpu_zoo_volumes.py,
+with a cache of their restated results.
+
+The volume-out and compose cases, and what each is for (measured CPU time of the restated answer beside it):
+  out_lattices()    every tree of ALL_TREES, chain14 included, on a depth-3 tree's lattice, one that sticks out of the cube on every
+                    side, one element, and DEEP_CORNER, 9^3 elements 2^-12 apart inside the chains' deepest cells (subnormal halves):
+                    under 0.1 s each
+  LONG_OUT          257^3 elements of blocks_1025, more than the 2^24 threads k_volume_out strides with; restated as slabs(0) and
+                    slabs(254), 0.7 s each (the whole lattice: 50 s)
+  COMPOSE_LISTS     csg (three ops on a depth-first tree, append order and the 12-deep chain: 0.1 s), keeps (the same as unions: the
+                    arrays grow once, under 1 s at depth 5), repeated (one handle four times), leaf_blocks (one node against a tree),
+                    chain14 (the walk over more than 12 levels, taken only with a depth given); each at COMPOSE_DEPTHS, 0.3 s at most
+Their far-corner, long-grid, negative-side, half-precision and 4096-instance companions need no zoo tree and live in
+tests/volume_cases.py and tests/compose_cases.py.
 
 _random_tree and _chain_tree are the generators of tests/test_gpu_parity.py, moved here unchanged: their code and the order of their
 RNG draws are what the parity fuzz seeds (the pinned seed 26 included) were found with."""
@@ -271,8 +284,10 @@ def place_args(name):
         return plr.IDENTITY, 1.0, (0.0, 0.0, 0.0)
     if name == "dyadic_075":
         return plr.IDENTITY, 0.75, (0.125, 0.0, 0.25)
-    assert name == "generic_half"
     import sdfbox_amd
+    if name == "turned_06":                                 # (the compositions' fourth: not among PLACE_NAMES)
+        return sdfbox_amd.placement(70, -25, 40, 0.6, to=(0.55, 0.45, 0.5))
+    assert name == "generic_half"
     return sdfbox_amd.placement(30, 20, 0, 0.5)
 
 
@@ -296,3 +311,65 @@ def restated_place(src, name, depth):
 def restated_measure(name, level):
     import measure_restatement as ms
     return restated(("measure", name, level), lambda: ms.measure(*zoo()[name], level, walked=walked(name)))
+
+
+# ---- the cases of volume out and compose (tests/test_zoo_volumes.py, tests/test_gpu_zoo_volumes.py) -------------------------------
+# Volume out reads EVERY tree, chain14 included (the look-up is the sampler's, which walks any consistent tree), on four lattices: a
+# depth-3 tree's own; one that sticks out of the cube on every side; one element; and 9^3 elements 2^-12 apart at the origin, inside the
+# chains' deepest cells.  Each restates in under 0.1 s.
+DEEP_CORNER = ((9, 9, 9), (0.0, 0.0, 0.0), 2.0 ** -12)
+# Past k_volume_out's 2^16 workgroups of 256 threads: 257^3 = 16 974 593 elements.  Its positions are exact in float32, so three slabs
+# of it are a lattice of their own, which restates in 0.7 s where the whole takes 50 s
+LONG_OUT = ((257, 257, 257), (0.0, 0.0, 0.0), 2.0 ** -8)
+LONG_OUT_SOURCE = "blocks_1025"
+
+
+def out_lattices():
+    from volume_cases import ONE, STICKS_OUT
+    return [((9, 9, 9), (0, 0, 0), 0.125), STICKS_OUT, ONE, DEEP_CORNER]
+
+
+def slabs(k0):
+    """three slabs of LONG_OUT from slab k0 on, as a lattice of their own"""
+    (nz, ny, nx), _, spacing = LONG_OUT
+    return ((3, ny, nx), (0.0, 0.0, k0 * spacing), spacing)
+
+
+def restated_out(name, lattice, dtype=np.float32):
+    """vr.volume_out of the zoo tree `name` on `lattice`; the float16 form is the float32 form's rounding, as vr.volume_out makes it"""
+    import volume_restatement as vr
+    full = restated(("out", name, lattice), lambda: vr.volume_out(zoo()[name], *lattice))
+    return full if np.dtype(dtype) == np.float32 else restated(("out16", name, lattice), lambda: full.astype(np.float16))
+
+
+# The compositions: name -> [(source, placement name, op)], each at COMPOSE_DEPTHS.  csg: depth-first, append order and the chain
+# under all three ops.  keeps: the same sources as unions, so that most of the tree stays and the result outgrows the arrays' start (1.5
+# times the sources together) once.  repeated: ONE handle in four instances.  leaf_blocks: one node against a tree.  chain14: the
+# 14-deep chain, which only a call with a depth given takes.
+_U, _I, _S = 0, 1, 2
+COMPOSE_DEPTHS = (4, 5)
+COMPOSE_LISTS = {
+    "csg": [("dfs_d6_a", "generic_half", _U), ("blocks_4097", "dyadic_075", _S), ("chain12", "identity", _I)],
+    "keeps": [("chain12", "identity", _U), ("blocks_4097", "dyadic_075", _U), ("dfs_d6_a", "generic_half", _U)],
+    "repeated": [("blocks_65", "identity", _U), ("blocks_65", "generic_half", _S), ("blocks_65", "dyadic_075", _U), ("blocks_65", "turned_06", _I)],
+    "leaf_blocks": [("leaf", "identity", _U), ("blocks_257", "generic_half", _S)],
+    "chain14": [("leaf", "identity", _U), ("chain14", "generic_half", _I)],
+}
+# the restatement's sizes at COMPOSE_DEPTHS (csg restates in 0.1 s, keeps at depth 5 in under 1 s: the build machine's CPU, as every time in this module)
+COMPOSE_NODES = {"csg": (1545, 3265), "keeps": (4169, 23625), "leaf_blocks": (1937, 7161), "chain14": (1129, 2001), "repeated": (2177, 6121)}
+
+
+def compose_cases():
+    """[(list name, depth)]"""
+    return [(name, d) for name in COMPOSE_LISTS for d in COMPOSE_DEPTHS]
+
+
+def compose_parts(name):
+    """[(source name, (R, s, t), op)]"""
+    return [(src, place_args(pl), op) for src, pl, op in COMPOSE_LISTS[name]]
+
+
+def restated_compose(name, depth):
+    """(structs, values, counts)"""
+    import compose_restatement as cpr
+    return restated(("compose", name, depth), lambda: cpr.compose([(zoo()[src], pl, op) for src, pl, op in compose_parts(name)], depth, want_counts=True))
