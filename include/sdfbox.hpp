@@ -166,8 +166,7 @@ public:
     {
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_upload(device, &model.Structs[0].Parent, model.Values.data(), (uint32_t)model.Length(), &fresh));
-        if (scene) sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // ... with the upload's choices taken by the host (sdfhip_upload_options: start from sdfhip_upload_options_default, -1 = choose):
     // e.g. top_grid_level = 0 for no lookup grid at all on a device short of memory
@@ -175,8 +174,7 @@ public:
     {
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_upload_ex(device, &model.Structs[0].Parent, model.Values.data(), (uint32_t)model.Length(), &options, &fresh));
-        if (scene) sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Space carving (sdfhip_scene_edit; the reference's README lists modeling under "Plans"): the brushes, in order, carve from or
     // add to the loaded model on its device, and the edited model replaces it as a reload does -- the old handle is freed once the
@@ -187,8 +185,7 @@ public:
         if (!scene) throw Error(SDFHIP_ERR_ARG, "Edit: no model loaded");
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_edit(scene, edits.data(), (uint32_t)edits.size(), max_depth, &fresh, host_out, stats));
-        sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Pruning (sdfhip_scene_prune): the blocks of eight that say nothing their parent does not already say -- within `tolerance` bytes
     // (0..255) of what the parent's bytes interpolate to, or below max_depth (-1 = no cut, else 0..12) -- are removed, and the
@@ -199,8 +196,7 @@ public:
         const sdfhip_prune_options opt = { (uint32_t)sizeof(sdfhip_prune_options), tolerance, max_depth };
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_prune(scene, &opt, &fresh, host_out, stats));
-        sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Combination (sdfhip_scene_combine): the loaded model becomes its union (SDFHIP_COMBINE_UNION), intersection (_INTERSECT) or
     // difference (_SUBTRACT: this model without the other) with the model `other` has loaded on the same device (it may be this
@@ -213,8 +209,7 @@ public:
         const sdfhip_combine_options opt = { (uint32_t)sizeof(sdfhip_combine_options), max_depth };
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_combine(scene, other.scene, op, &opt, &fresh, host_out, stats));
-        sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Placement (sdfhip_scene_place): the loaded model is rotated, scaled and moved -- a point x of it lands at scale * R x + t, R
     // row-major and orthogonal (a mirror is allowed), scale > 0 -- by resampling it into a new tree of at most `depth` levels (-1 = the
@@ -234,8 +229,7 @@ public:
         pl.depth = depth;
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_place(scene, &pl, &fresh, host_out, stats));
-        sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Composition (sdfhip_scene_compose): the model becomes ONE tree made of many placed instances of the models that Programs on
     // this device have loaded (this one may be among them, and the same Program may appear in many parts), in a single pass: part
@@ -268,8 +262,7 @@ public:
         const sdfhip_compose_options opt = { (uint32_t)sizeof(sdfhip_compose_options), depth };
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_compose(list.data(), (uint32_t)list.size(), &opt, &fresh, host_out, stats));
-        if (scene) sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
     // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at
@@ -284,8 +277,7 @@ public:
         const sdfhip_volume vol = Lattice(n, origin, spacing, value_scale, depth);
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_volume_build(device, grid.data(), &vol, &fresh, host_out, stats));
-        if (scene) sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     std::vector<float> Volume(const uint32_t (&n)[3], const float (&origin)[3], float spacing)
     {
@@ -336,8 +328,7 @@ public:
         opt.level_b = other_level;
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_blend(scene, other.scene, &opt, &fresh, host_out, stats));
-        sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     void Morph(const Program &other, float t, int depth = -1, int level = -1, int other_level = -1, sdfhip_blend_stats *stats = nullptr,
                sdfhip_octdata *host_out = nullptr)
@@ -411,8 +402,7 @@ public:
         struct Release { sdfhip_trimesh &m; ~Release() { sdfhip_trimesh_free(&m); } } release{ mesh };
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_trimesh_build(device, &mesh, depth, &fresh, nullptr, stats));
-        if (scene) sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
     // Draw's UpdateBuffer(info) + DispatchSized(W, H, 1), Program.cs:81,94 -> RGBA32F frame
     void Draw(const Info &state, int width, int height, std::vector<float> &frame, uint32_t flags = 0)
@@ -430,6 +420,12 @@ public:
     }
 
 private:
+    // the reload swap: the new model exists, so drop the loaded one (if any) and take it
+    void Adopt(sdfhip_scene *fresh)
+    {
+        if (scene) sdfhip_scene_free(scene);
+        scene = fresh;
+    }
     static sdfhip_volume Lattice(const uint32_t (&n)[3], const float (&origin)[3], float spacing, float value_scale, int depth)
     {
         sdfhip_volume v = {};
@@ -452,8 +448,7 @@ private:
         opt.level = level;
         sdfhip_scene *fresh = nullptr;
         Check(sdfhip_scene_offset(scene, &opt, &fresh, host_out, stats));
-        sdfhip_scene_free(scene);
-        scene = fresh;
+        Adopt(fresh);
     }
 
     int device;

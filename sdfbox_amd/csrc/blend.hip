@@ -70,21 +70,16 @@ try {
     const float amount = opt->amount;
     const bool one_bitmap = a == b && opt->level_a == opt->level_b;
 
-    DeviceGuard g(A.device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "%s: hipSetDevice(%d) failed", what, A.device);
-    DeviceBuffers bufs("SDFHIP_BLEND_FAIL_ALLOC");
-    CallStream<2> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-
+    CallFrame<2> call(what, A.device, "SDFHIP_BLEND_FAIL_ALLOC", t0);
+    DeviceBuffers &bufs = call.bufs;
     LevelBuild R;
     unsigned long long visited[2] = { 0, 0 };
-    try {
+    if (const int rc = call.run("both operands are untouched", [&](hipStream_t st) -> int {
         uint32_t *below_a = bufs.get<uint32_t>(bitmap_words(A.Q.n_nodes));
         uint32_t *below_b = one_bitmap ? below_a : bufs.get<uint32_t>(bitmap_words(B.Q.n_nodes));
         unsigned long long *d_visited = bufs.get<unsigned long long>(2);
         HIP_TRY(hipMemsetAsync(d_visited, 0, 2 * sizeof *d_visited, st));
-        HIP_TRY(hipEventRecord(cs.ev[0], st));
+        HIP_TRY(hipEventRecord(call.cs.ev[0], st));
         if (const int rc = launch_mark(A, opt->level_a, below_a, st)) return rc;
         if (!one_bitmap)
             if (const int rc = launch_mark(B, opt->level_b, below_b, st)) return rc;
@@ -105,23 +100,21 @@ try {
         // (the arrays start from the two operands' sizes together)
         const uint32_t nodes_in = (uint32_t)std::min<uint64_t>((uint64_t)A.Q.n_nodes + B.Q.n_nodes, 0x7FFFFFFFull);
         if (const int rc = build_levels(what, bufs, st, nodes_in, depth, level, R)) return rc;
-        HIP_TRY(hipEventRecord(cs.ev[1], st));
+        HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         HIP_TRY(hipMemcpyAsync(visited, d_visited, sizeof visited, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory (both operands are untouched)", what);
-    }
-    float kernel_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, cs.ev[0], cs.ev[1]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree(what, A.device, R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
+    float kernel_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&kernel_ms, 0, 1)) return rc;
+    if (const int rc = call.finish(R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_a = A.Q.n_nodes; stats->nodes_b = B.Q.n_nodes; stats->nodes_out = R.n_out; stats->depth_out = R.depth_out;
         stats->levels = R.depth_out + 1; stats->pad0_ = 0;
         stats->points = R.points; stats->visited_a = visited[0]; stats->visited_b = visited[1];
         stats->kernel_ms = kernel_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
         stats->pad_ = 0;
     }
     return SDFHIP_OK;

@@ -79,12 +79,8 @@ try {
             return fail(SDFHIP_ERR_BAD_TREE, "scene_combine: operand %s is not a consistent tree (or deeper than %d levels): no combination",
                         x == &A ? "a" : "b", TREE_MAX_DEPTH);
 
-    DeviceGuard g(A.device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_combine: hipSetDevice(%d) failed", A.device);
-    DeviceBuffers bufs("SDFHIP_COMBINE_FAIL_ALLOC");
-    CallStream<2> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
+    CallFrame<2> call("scene_combine", A.device, "SDFHIP_COMBINE_FAIL_ALLOC", t0);
+    DeviceBuffers &bufs = call.bufs;
 
     const uint32_t nA = A.n, nB = B.n;
     // nothing is pruned and nothing invented: every result node is a node of A or of B, and the root is one of both; under a cut, no
@@ -95,7 +91,7 @@ try {
     const uint32_t words = 2 * ((cap + 63) / 64), nchunk_max = (words + 1023) / 1024;
     uint32_t n_out = 1, depth_out = 0, shared = 0;
     int2 *dS = nullptr; uint2 *dV = nullptr;
-    try {
+    if (const int rc = call.run("both operands are untouched", [&](hipStream_t st) -> int {
         dS = bufs.get<int2>(cap);
         dV = bufs.get<uint2>(cap);
         CombineItem *items = bufs.get<CombineItem>(cap);
@@ -105,7 +101,7 @@ try {
         uint32_t *shared_count = bufs.get<uint32_t>(1);
         HIP_TRY(hipMemsetAsync(shared_count, 0, sizeof(uint32_t), st));
 
-        HIP_TRY(hipEventRecord(cs.ev[0], st));
+        HIP_TRY(hipEventRecord(call.cs.ev[0], st));
         hipLaunchKernelGGL(k_combine_root, dim3(1), dim3(64), 0, st, A.nodes, B.nodes, items, dS);
         HIP_TRY(hipGetLastError());
         uint32_t first = 0, n = 1;
@@ -137,22 +133,20 @@ try {
             n = 8u * n_split;
             n_out = (uint32_t)total;
         }
-        HIP_TRY(hipEventRecord(cs.ev[1], st));
+        HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         HIP_TRY(hipMemcpyAsync(&shared, shared_count, sizeof shared, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "scene_combine: out of device memory (both operands are untouched)");
-    }
-    float kernel_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, cs.ev[0], cs.ev[1]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree("scene_combine", A.device, dS, dV, n_out, (int)depth_out, out, host_out, &scene_ms)) return rc;
+    float kernel_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&kernel_ms, 0, 1)) return rc;
+    if (const int rc = call.finish(dS, dV, n_out, (int)depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_a = nA; stats->nodes_b = nB; stats->nodes_out = n_out; stats->depth_out = depth_out;
         stats->nodes_shared = shared;
         stats->kernel_ms = kernel_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
     }
     return SDFHIP_OK;
 }

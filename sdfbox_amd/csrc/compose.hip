@@ -75,7 +75,7 @@ try {
     // What the call uses of each distinct handle is read under that handle's lock, one handle after the other and never two locks
     // at once, and the lock is released before any work is issued, as sdfhip_scene_place does: the records are only ever read.
     std::vector<std::pair<const sdfhip_scene *, Source>> sources;
-    std::vector<ComposeInstance> table(n_instances);          // (before `bufs` and `cs`: alive until the stream that copies it is drained)
+    std::vector<ComposeInstance> table(n_instances);          // (before `call`: alive until the stream that copies it is drained)
     uint64_t nodes_sum = 0;
     uint32_t deepest = 0;
     for (uint32_t k = 0; k < n_instances; k++) {
@@ -106,39 +106,31 @@ try {
     const int depth = depth_opt < 0 ? (int)deepest : depth_opt;
     const int device = sources.front().second.device;
 
-    DeviceGuard g(device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_compose: hipSetDevice(%d) failed", device);
-    DeviceBuffers bufs("SDFHIP_COMPOSE_FAIL_ALLOC");
-    CallStream<2> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-
+    CallFrame<2> call("scene_compose", device, "SDFHIP_COMPOSE_FAIL_ALLOC", t0);
     LevelBuild R;
-    try {
-        ComposeInstance *d_table = bufs.get<ComposeInstance>(n_instances);
+    if (const int rc = call.run("the sources are untouched", [&](hipStream_t st) -> int {
+        ComposeInstance *d_table = call.bufs.get<ComposeInstance>(n_instances);
         HIP_TRY(hipMemcpyAsync(d_table, table.data(), n_instances * sizeof(ComposeInstance), hipMemcpyHostToDevice, st));
         const auto level = [&](const LevelBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
             hipLaunchKernelGGL(k_compose_level, grid_stride_blocks(64ull * nblocks, LEVEL_MAX_WORKGROUPS), dim3(LEVEL_THREADS), 0, st, d_table, n_instances,
                                blocks, nblocks, nchild, S, may_split, V, split);
         };
-        // (the arrays start from the distinct sources' sizes together; kernel_ms starts once the first of them are there: cs.ev[0])
+        // (the arrays start from the distinct sources' sizes together; kernel_ms starts once the first of them are there: ev[0])
         const uint32_t nodes_in = (uint32_t)std::min<uint64_t>(nodes_sum, 0x7FFFFFFFull);
-        if (const int rc = build_levels("scene_compose", bufs, st, nodes_in, depth, level, R, cs.ev[0])) return rc;
-        HIP_TRY(hipEventRecord(cs.ev[1], st));
+        if (const int rc = build_levels(call.what, call.bufs, st, nodes_in, depth, level, R, call.cs.ev[0])) return rc;
+        HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "scene_compose: out of device memory (the sources are untouched)");
-    }
-    float kernel_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, cs.ev[0], cs.ev[1]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree("scene_compose", device, R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
+    float kernel_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&kernel_ms, 0, 1)) return rc;
+    if (const int rc = call.finish(R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_out = R.n_out; stats->depth_out = R.depth_out; stats->levels = R.depth_out + 1; stats->instances = n_instances;
         stats->samples = (uint64_t)n_instances * R.points;
         stats->kernel_ms = kernel_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
         stats->pad_ = 0;
     }
     return SDFHIP_OK;

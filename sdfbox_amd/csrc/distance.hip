@@ -119,25 +119,18 @@ try {
     const Source src = read_source(scene);
     if (const int rc = check_source(what, src)) return rc;
     if (n == 0) return SDFHIP_OK;
-    DeviceGuard g(src.device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "%s: hipSetDevice(%d) failed", what, src.device);
-    DeviceBuffers bufs("SDFHIP_DISTANCE_FAIL_ALLOC");
-    CallStream<1> cs;                      // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-    try {
-        float *d_xyz = bufs.get<float>(3 * (size_t)n);
-        sdfhip_clearance *d_out = bufs.get<sdfhip_clearance>(n);
-        uint32_t *below = bufs.get<uint32_t>(bitmap_words(src.Q.n_nodes));
+    CallFrame<1> call(what, src.device, "SDFHIP_DISTANCE_FAIL_ALLOC");
+    return call.run("the scene is untouched", [&](hipStream_t st) -> int {
+        float *d_xyz = call.bufs.get<float>(3 * (size_t)n);
+        sdfhip_clearance *d_out = call.bufs.get<sdfhip_clearance>(n);
+        uint32_t *below = call.bufs.get<uint32_t>(bitmap_words(src.Q.n_nodes));
         HIP_TRY(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
         if (const int rc = launch_mark(src, level, below, st)) return rc;
         if (const int rc = launch_query(src, DistScene{src.Q.nodes, src.Q.n_nodes, below, level}, d_xyz, n, d_out, st)) return rc;
         HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(sdfhip_clearance), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory (the scene is untouched)", what);
-    }
-    return SDFHIP_OK;
+        return SDFHIP_OK;
+    });
 }
 SDFHIP_ABI_CATCH(sdfhip_scene_distance)
 
@@ -159,42 +152,34 @@ try {
     const int mode = opt->mode;
     const float amount = mode == SDFHIP_OFFSET_SHELL ? opt->amount * 0.5f : opt->amount;
 
-    DeviceGuard g(src.device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "%s: hipSetDevice(%d) failed", what, src.device);
-    DeviceBuffers bufs("SDFHIP_OFFSET_FAIL_ALLOC");
-    CallStream<2> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-
+    CallFrame<2> call(what, src.device, "SDFHIP_OFFSET_FAIL_ALLOC", t0);
     LevelBuild R;
     unsigned long long visited = 0;
-    try {
-        uint32_t *below = bufs.get<uint32_t>(bitmap_words(src.Q.n_nodes));
-        unsigned long long *d_visited = bufs.get<unsigned long long>(1);
+    if (const int rc = call.run("the source is untouched", [&](hipStream_t st) -> int {
+        uint32_t *below = call.bufs.get<uint32_t>(bitmap_words(src.Q.n_nodes));
+        unsigned long long *d_visited = call.bufs.get<unsigned long long>(1);
         HIP_TRY(hipMemsetAsync(d_visited, 0, sizeof *d_visited, st));
-        HIP_TRY(hipEventRecord(cs.ev[0], st));
+        HIP_TRY(hipEventRecord(call.cs.ev[0], st));
         if (const int rc = launch_mark(src, opt->level, below, st)) return rc;
         const DistScene D{src.Q.nodes, src.Q.n_nodes, below, opt->level};
         const auto level = [&](const LevelBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
             launch_level(src, D, mode, amount, blocks, nblocks, nchild, S, may_split, V, split, d_visited, st);
         };
-        if (const int rc = build_levels(what, bufs, st, src.Q.n_nodes, depth, level, R)) return rc;
-        HIP_TRY(hipEventRecord(cs.ev[1], st));
+        if (const int rc = build_levels(what, call.bufs, st, src.Q.n_nodes, depth, level, R)) return rc;
+        HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         HIP_TRY(hipMemcpyAsync(&visited, d_visited, sizeof visited, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory (the source is untouched)", what);
-    }
-    float kernel_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, cs.ev[0], cs.ev[1]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree(what, src.device, R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
+    float kernel_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&kernel_ms, 0, 1)) return rc;
+    if (const int rc = call.finish(R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_in = src.Q.n_nodes; stats->nodes_out = R.n_out; stats->depth_out = R.depth_out; stats->levels = R.depth_out + 1;
         stats->points = R.points; stats->visited = visited;
         stats->kernel_ms = kernel_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
         stats->pad_ = 0;
     }
     return SDFHIP_OK;

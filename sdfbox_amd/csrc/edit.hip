@@ -61,20 +61,15 @@ try {
         return fail(SDFHIP_ERR_BAD_TREE, "scene_edit: the input tree is not consistent (or deeper than %d levels): no edit", TREE_MAX_DEPTH);
     const int maxd = max_depth < 0 ? (int)scene->depth : max_depth;
 
-    DeviceGuard g(scene->device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_edit: hipSetDevice(%d) failed", scene->device);
-    DeviceBuffers ws("SDFHIP_EDIT_FAIL_ALLOC");
-    CallStream<2> cs;                       // (after `ws`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-    const hipEvent_t ev0 = cs.ev[0], ev1 = cs.ev[1];
+    CallFrame<2> call("scene_edit", scene->device, "SDFHIP_EDIT_FAIL_ALLOC", t0);
+    DeviceBuffers &ws = call.bufs;
 
     uint64_t n_cur = scene->n;
     uint32_t depth_out = scene->depth;
     uint64_t visited = 0, changed = 0, blocks = 0;
     int2 *dS = nullptr; uint2 *dV = nullptr;
     size_t cap_nodes = 0;
-    try {
+    if (const int rc = call.run("the input scene is untouched", [&](hipStream_t st) -> int {
         // the arrays: the input's records, unfused, with room to grow
         cap_nodes = (size_t)n_cur + (n_cur >> 4) + 4096;
         dS = ws.get<int2>(cap_nodes);
@@ -85,7 +80,7 @@ try {
         size_t c_fr_cur = 0, c_fr_next = 0, c_splits = 0, c_par_cur = 0, c_par_next = 0, c_bitmap = 0, c_pre = 0, c_chunk = 0;
         EditCounters *cnt = ws.get<EditCounters>(EDIT_LEVELS);
 
-        HIP_TRY(hipEventRecord(ev0, st));
+        HIP_TRY(hipEventRecord(call.cs.ev[0], st));
         hipLaunchKernelGGL(k_edit_unfuse, grid_stride_blocks(n_cur, 8192), dim3(256), 0, st, scene->nodes, dS, dV, (uint32_t)n_cur);
         HIP_TRY(hipGetLastError());
         for (uint32_t ei = 0; ei < n_edits; ei++) {
@@ -159,23 +154,21 @@ try {
                 std::swap(fr_cur, fr_next); std::swap(c_fr_cur, c_fr_next);
             }
         }
-        HIP_TRY(hipEventRecord(ev1, st));
+        HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "scene_edit: out of device memory (the input scene is untouched)");
-    }
-    float edit_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&edit_ms, ev0, ev1));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree("scene_edit", scene->device, dS, dV, (uint32_t)n_cur, (int)depth_out, out, host_out, &scene_ms)) return rc;
+    float edit_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&edit_ms, 0, 1)) return rc;
+    if (const int rc = call.finish(dS, dV, (uint32_t)n_cur, (int)depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_in = scene->n; stats->nodes_out = (uint32_t)n_cur;
         stats->nodes_visited = (uint32_t)std::min<uint64_t>(visited, 0xFFFFFFFFu);
         stats->nodes_changed = (uint32_t)std::min<uint64_t>(changed, 0xFFFFFFFFu);
         stats->blocks_added = (uint32_t)blocks; stats->depth_out = depth_out;
         stats->edit_ms = edit_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
     }
     return SDFHIP_OK;
 }

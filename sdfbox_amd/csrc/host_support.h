@@ -1,6 +1,7 @@
 // What the host side of libsdfhip.so shares beyond the scene handle: the HIP_TRY prefix form, growable buffers, the builders' arenas,
-// and the call frame of the tree rewriters (edit.hip, prune.hip, trigen.hip: NoMem, AllocFault, DeviceBuffers, CallStream,
-// finish_tree).  Not one of the renderer's measured sources (bench_report.py
+// and the call frame of the calls that build a tree on the device (NoMem, AllocFault, DeviceBuffers, CallStream, finish_tree, and
+// CallFrame, which holds them for edit.hip, prune.hip, combine.hip, place.hip, compose.hip, volume.hip, distance.hip and blend.hip;
+// trigen.hip brings arenas of its own to the same parts).  Not one of the renderer's measured sources (bench_report.py
 // hashes scene.h, which this header includes and which must never include it): a helper a new translation unit needs goes here.
 #pragma once
 #include "scene.h"
@@ -108,7 +109,7 @@ struct Arena {
     ~Arena() { for (auto &c : chunks) pool_give(device, c.base, c.size); }
 };
 
-// ---- the call frame of the calls that turn a tree on the device into a new scene (edit.hip, prune.hip, trigen.hip) ---------------
+// ---- the call frame of the calls that turn a tree on the device into a new scene (CallFrame's users, trigen.hip) -----------------
 
 constexpr int TREE_MAX_DEPTH = 12;          // LM: the deepest tree the grids and the cursor-stack kernels take
 
@@ -163,9 +164,9 @@ struct DeviceBuffers {
     }
 };
 
-// A call's own non-blocking stream and N timing events.  The destructor waits for the stream before it destroys anything, so
-// DECLARE IT AFTER the call's DeviceBuffers / arenas: locals die in reverse order, and the stream must be drained before the memory
-// its kernels use is freed (or goes back to the pool) on whatever path the call returns.
+// A call's own non-blocking stream and N timing events.  The destructor waits for the stream before it destroys anything, so it
+// is declared after the call's memory (CallFrame's members; trigen.hip's arenas): the stream must be drained before the memory its
+// kernels use is freed (or goes back to the pool) on whatever path the call returns.
 template <int N> struct CallStream {
     hipStream_t st = nullptr;
     hipEvent_t ev[N] = {};
@@ -218,5 +219,36 @@ inline int finish_tree(const char *what, int device, const int2 *dS, const uint2
     if (scene) *scene = res;
     return SDFHIP_OK;
 }
+
+// What a call that builds on `device` holds from its last refusal on, once: what: the entry point's name as its messages begin;
+// fault_variable: DeviceBuffers'; t0: the call's first line.  The members in this order: whichever way the call returns, the
+// stream is drained, then the buffers are freed, then the caller's device is restored.
+template <int N> struct CallFrame {
+    const char *what;
+    int device;
+    std::chrono::steady_clock::time_point t0;
+    DeviceGuard guard;
+    DeviceBuffers bufs;
+    CallStream<N> cs;
+    CallFrame(const char *what, int device, const char *fault_variable, std::chrono::steady_clock::time_point t0 = {})
+        : what(what), device(device), t0(t0), guard(device), bufs(fault_variable) {}
+    // Opens the stream and runs body(stream), the call's passes.  untouched: what a call that ran out of memory says it has left
+    // as it was ("the source is untouched").
+    template <class Body> int run(const char *untouched, Body body)
+    try {
+        if (!guard.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "%s: hipSetDevice(%d) failed", what, device);
+        if (const int rc = cs.open("")) return rc;
+        return body(cs.st);
+    } catch (const NoMem &) {
+        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory (%s)", what, untouched);
+    }
+    // the time between two of the call's events, both recorded and reached
+    int elapsed(float *ms, int from, int to) const { HIP_TRY(hipEventElapsedTime(ms, cs.ev[from], cs.ev[to])); return SDFHIP_OK; }
+    int finish(const int2 *dS, const uint2 *dV, uint32_t n, int depth, sdfhip_scene **scene, sdfhip_octdata *host_out, float *scene_ms) const
+    {
+        return finish_tree(what, device, dS, dV, n, depth, scene, host_out, scene_ms);
+    }
+    float total_ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
 
 }  // namespace sdfhip

@@ -1,5 +1,5 @@
-// The host side that every lattice builder shares: place.hip (sdfhip_scene_place), distance.hip (sdfhip_scene_offset) and blend.hip
-// (sdfhip_scene_blend).  What a call reads of a handle, the cursor a look-up takes, and the level loop (build_levels: a template on
+// The host side that every lattice builder shares: place.hip (sdfhip_scene_place), compose.hip (sdfhip_scene_compose), volume.hip
+// (sdfhip_volume_build), distance.hip (sdfhip_scene_offset) and blend.hip (sdfhip_scene_blend).  What a call reads of a handle, the cursor a look-up takes, and the level loop (build_levels: a template on
 // the launch of a level's first pass, so each caller brings its own kernel round level_kernels.h's level_body; the shared bitmap
 // scan and k_level_emit do the rest).  Everything here is inline or a template.  What only the builders on the exact distance need
 // -- their refusals, the "surface below" bitmap -- is distance_host.h's.

@@ -68,38 +68,30 @@ try {
     M.s = pl->scale; M.inv = 1.0f / pl->scale;
     M.tx = pl->translation[0]; M.ty = pl->translation[1]; M.tz = pl->translation[2];
 
-    DeviceGuard g(src.device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_place: hipSetDevice(%d) failed", src.device);
-    DeviceBuffers bufs("SDFHIP_PLACE_FAIL_ALLOC");
-    CallStream<2> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-
+    CallFrame<2> call("scene_place", src.device, "SDFHIP_PLACE_FAIL_ALLOC", t0);
     LevelBuild R;
-    try {
+    if (const int rc = call.run("the source is untouched", [&](hipStream_t st) -> int {
         const auto level = [&](const LevelBlock *blocks, uint32_t nblocks, uint32_t nchild, float S, int may_split, uint2 *V, uint8_t *split) {
             with_cursor(src.form, [&](auto c) {
                 hipLaunchKernelGGL((k_place_level<typename decltype(c)::type>), grid_stride_blocks(64ull * nblocks, LEVEL_MAX_WORKGROUPS), dim3(LEVEL_THREADS), 0, st,
                                    src.Q, M, blocks, nblocks, nchild, S, may_split, V, split);
             });
         };
-        // (nothing is allocated before the loop's own arrays; kernel_ms starts once the first of them are there: cs.ev[0])
-        if (const int rc = build_levels("scene_place", bufs, st, src.Q.n_nodes, depth, level, R, cs.ev[0])) return rc;
-        HIP_TRY(hipEventRecord(cs.ev[1], st));
+        // (nothing is allocated before the loop's own arrays; kernel_ms starts once the first of them are there: ev[0])
+        if (const int rc = build_levels(call.what, call.bufs, st, src.Q.n_nodes, depth, level, R, call.cs.ev[0])) return rc;
+        HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "scene_place: out of device memory (the source is untouched)");
-    }
-    float kernel_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, cs.ev[0], cs.ev[1]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree("scene_place", src.device, R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
+    float kernel_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&kernel_ms, 0, 1)) return rc;
+    if (const int rc = call.finish(R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_in = src.Q.n_nodes; stats->nodes_out = R.n_out; stats->depth_out = R.depth_out; stats->levels = R.depth_out + 1;
         stats->samples = R.points;
         stats->kernel_ms = kernel_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
         stats->pad_ = 0;
     }
     return SDFHIP_OK;

@@ -66,20 +66,16 @@ try {
     if (!scene->stack_ok || scene->depth > (uint32_t)TREE_MAX_DEPTH)
         return fail(SDFHIP_ERR_BAD_TREE, "scene_prune: the input tree is not consistent (or deeper than %d levels): no prune", TREE_MAX_DEPTH);
 
-    DeviceGuard g(scene->device);
-    if (!g.ok) return (void)hipGetLastError(), fail(SDFHIP_ERR_DEVICE, "scene_prune: hipSetDevice(%d) failed", scene->device);
-    DeviceBuffers bufs("SDFHIP_PRUNE_FAIL_ALLOC");
-    CallStream<4> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
-    const hipEvent_t *ev = cs.ev;
+    CallFrame<4> call("scene_prune", scene->device, "SDFHIP_PRUNE_FAIL_ALLOC", t0);
+    DeviceBuffers &bufs = call.bufs;
+    const hipEvent_t *ev = call.cs.ev;
 
     const uint32_t n = scene->n;
     const uint32_t cap = (n - 1) / 8;                       // a consistent tree's internal nodes: every other node lies in one's block
     const uint32_t words = (n + 31) / 32, nchunk = (words + 1023) / 1024;
     uint32_t n_out = 0, depth_out = 0, blocks_removed = 0;
     int2 *dS = nullptr; uint2 *dV = nullptr;
-    try {
+    if (const int rc = call.run("the input scene is untouched", [&](hipStream_t st) -> int {
         uint32_t *list = bufs.get<uint32_t>(cap);
         uint32_t *removed = bufs.get<uint32_t>((size_t)words + 1);        // (+ 1: a block's byte may straddle the last word's end)
         uint32_t *pre = bufs.get<uint32_t>(words);
@@ -142,20 +138,18 @@ try {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[3], st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "scene_prune: out of device memory (the input scene is untouched)");
-    }
-    float ms_a = 0.0f, ms_b = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms_a, ev[0], ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms_b, ev[2], ev[3]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree("scene_prune", scene->device, dS, dV, n_out, (int)depth_out, out, host_out, &scene_ms)) return rc;
+    float ms_a = 0.0f, ms_b = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&ms_a, 0, 1)) return rc;
+    if (const int rc = call.elapsed(&ms_b, 2, 3)) return rc;
+    if (const int rc = call.finish(dS, dV, n_out, (int)depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_in = n; stats->nodes_out = n_out;
         stats->blocks_removed = blocks_removed; stats->depth_out = depth_out;
         stats->kernel_ms = ms_a + ms_b; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
     }
     return SDFHIP_OK;
 }

@@ -76,13 +76,12 @@ int build_as(const char *what, int device, const void *grid, bool on_device, con
              sdfhip_octdata *host_out, sdfhip_volume_stats *stats, std::chrono::steady_clock::time_point t0)
 {
     const VolumeGrid G = grid_of_record(vol);
-    DeviceBuffers bufs("SDFHIP_VOLUME_FAIL_ALLOC");
-    CallStream<4> cs;                       // (after `bufs`: drained before the buffers are freed)
-    if (const int rc = cs.open("")) return rc;
-    const hipStream_t st = cs.st;
+    CallFrame<4> call(what, device, "SDFHIP_VOLUME_FAIL_ALLOC", t0);
+    DeviceBuffers &bufs = call.bufs;
+    const CallStream<4> &cs = call.cs;
 
     LevelBuild R;
-    try {
+    if (const int rc = call.run("the grid is untouched", [&](hipStream_t st) -> int {
         const T *d_grid = static_cast<const T *>(grid);
         if (!on_device) {
             T *staged = bufs.get<T>((size_t)total);
@@ -113,20 +112,18 @@ int build_as(const char *what, int device, const void *grid, bool on_device, con
         if (const int rc = build_levels(what, bufs, st, start, vol->depth, level, R, cs.ev[2])) return rc;
         HIP_TRY(hipEventRecord(cs.ev[3], st));
         HIP_TRY(hipStreamSynchronize(st));
-    } catch (const NoMem &) {
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory (the grid is untouched)", what);
-    }
-    float check_ms = 0.0f, kernel_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&check_ms, cs.ev[0], cs.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, cs.ev[2], cs.ev[3]));
+        return SDFHIP_OK;
+    })) return rc;
 
-    float scene_ms = 0.0f;
-    if (const int rc = finish_tree(what, device, R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
+    float check_ms = 0.0f, kernel_ms = 0.0f, scene_ms = 0.0f;
+    if (const int rc = call.elapsed(&check_ms, 0, 1)) return rc;
+    if (const int rc = call.elapsed(&kernel_ms, 2, 3)) return rc;
+    if (const int rc = call.finish(R.dS, R.dV, R.n_out, (int)R.depth_out, out, host_out, &scene_ms)) return rc;
     if (stats) {
         stats->nodes_out = R.n_out; stats->depth_out = R.depth_out; stats->levels = R.depth_out + 1; stats->pad_ = 0;
         stats->samples = R.points;
         stats->check_ms = check_ms; stats->kernel_ms = kernel_ms; stats->scene_ms = scene_ms;
-        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = call.total_ms();
     }
     return SDFHIP_OK;
 }
@@ -146,8 +143,6 @@ int build(const char *what, int device, const void *grid, bool on_device, const 
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(SDFHIP_ERR_DEVICE, "%s: device %d of %d does not exist", what, device, ndev);
-    DeviceGuard g(device);
-    if (!g.ok) return fail(SDFHIP_ERR_DEVICE, "%s: hipSetDevice(%d) failed", what, device);
     if (vol->dtype == SDFHIP_VOLUME_F16) return build_as<__half>(what, device, grid, on_device, vol, total, out, host_out, stats, t0);
     return build_as<float>(what, device, grid, on_device, vol, total, out, host_out, stats, t0);
 }

@@ -177,71 +177,54 @@ class Scene:
         self.top_grid_level, self.top_grid_bytes = lvl.value, nb.value
 
     @classmethod
-    def FromPoints(cls, vertices, depth, device=0, want_octdata=False, want_stats=False):
-        """The viewer's generate -> upload flow in one call (sdfhip_sdfgen_scene; Program.cs:613-650 + :147-152): point
-        cloud (n, 6) float32 {position, normal} -> scene handle, the tree never leaving HBM.  want_octdata: also the host
-        arrays (for the .asdf cache)."""
+    def _built(cls, device, st, call, want_octdata, want_stats, want_scene=True):
+        """The frame of every call that returns a new tree.  call(handle, octdata, stats): a lambda round the library's entry point,
+        which gets the three byref()s: the new handle (None with want_scene False: TriMesh.Build), the host arrays (None unless
+        wanted) and the stats record `st`.  Returns the new Scene, or (scene[, octdata][, stats])."""
         from .octdata import OctData
-        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 6)
         self = cls.__new__(cls)
         self._h = ctypes.c_void_p()
         self.device = int(device)
         raw = _lib.COctData()
-        st = _lib.SdfGenStats()
-        check(lib.sdfhip_sdfgen_scene(self.device, v.ctypes.data, len(v), int(depth), ctypes.byref(self._h),
-                                      ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        self._describe()
-        out = [self]
+        check(call(ctypes.byref(self._h) if want_scene else None, ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+        out = []
+        if want_scene:
+            self._describe()
+            out.append(self)
         if want_octdata:
             out.append(OctData._from_native(raw))
         if want_stats:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
+
+    @classmethod
+    def FromPoints(cls, vertices, depth, device=0, want_octdata=False, want_stats=False):
+        """The viewer's generate -> upload flow in one call (sdfhip_sdfgen_scene; Program.cs:613-650 + :147-152): point
+        cloud (n, 6) float32 {position, normal} -> scene handle, the tree never leaving HBM.  want_octdata: also the host
+        arrays (for the .asdf cache)."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 6)
+        return cls._built(device, _lib.SdfGenStats(), lambda h, raw, st: lib.sdfhip_sdfgen_scene(int(device), v.ctypes.data, len(v), int(depth), h, raw, st),
+                          want_octdata, want_stats)
 
     def Edit(self, edits, max_depth=None, want_octdata=False, want_stats=False):
         """Space carving (sdfhip_scene_edit): the brushes `edits` -- Edit objects, or (op, brush, params) tuples, applied in order --
         carve from (EDIT_CARVE) or add to (EDIT_ADD) this scene's tree on its device; the result is a NEW Scene, this one is left as
         it was.  max_depth: None = this tree's depth, else 0..12 (deeper lets the brushes refine past it).  want_octdata: also the
         result's host arrays (e.g. for OctData.Save); want_stats: an EditStats."""
-        from .octdata import OctData
         items = [e if isinstance(e, _lib.Edit) else _lib.Edit(*e) for e in edits]
         arr = (_lib.Edit * max(1, len(items)))(*items)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = self.device
-        raw = _lib.COctData()
-        st = _lib.EditStats()
-        check(lib.sdfhip_scene_edit(self._h, arr, len(items), -1 if max_depth is None else int(max_depth), ctypes.byref(res._h),
-                                    ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        maxd = -1 if max_depth is None else int(max_depth)
+        return Scene._built(self.device, _lib.EditStats(), lambda h, raw, st: lib.sdfhip_scene_edit(self._h, arr, len(items), maxd, h, raw, st),
+                            want_octdata, want_stats)
 
     def Prune(self, tolerance=0, max_depth=None, want_octdata=False, want_stats=False):
         """Pruning (sdfhip_scene_prune): the blocks of eight whose bytes are, within `tolerance` (0..255), what their parent's bytes
         interpolate to -- what Edit gave them before a brush touched them -- are removed, bottom-up, and with max_depth (None = no
         cut, else 0..12) every block below that depth; the result is a NEW Scene, this one is left as it was.  want_octdata: also
         the result's host arrays; want_stats: a PruneStats."""
-        from .octdata import OctData
         opt = _lib.PruneOptions(tolerance, max_depth)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = self.device
-        raw = _lib.COctData()
-        st = _lib.PruneStats()
-        check(lib.sdfhip_scene_prune(self._h, ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None,
-                                     ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(self.device, _lib.PruneStats(), lambda h, raw, st: lib.sdfhip_scene_prune(self._h, ctypes.byref(opt), h, raw, st),
+                            want_octdata, want_stats)
 
     def Combine(self, other, op, max_depth=None, want_octdata=False, want_stats=False):
         """Combination (sdfhip_scene_combine): the union (COMBINE_UNION), intersection (COMBINE_INTERSECT) or difference
@@ -249,22 +232,9 @@ class Scene:
         live in the same unit cube, nothing is placed, blended or pruned (chain Prune(0)).  max_depth: None = no cut, else 0..12.
         The result is a NEW Scene in breadth-first order, both inputs are left as they were.  want_octdata: also the result's host
         arrays; want_stats: a CombineStats."""
-        from .octdata import OctData
         opt = _lib.CombineOptions(max_depth)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = self.device
-        raw = _lib.COctData()
-        st = _lib.CombineStats()
-        check(lib.sdfhip_scene_combine(self._h, other._h, int(op), ctypes.byref(opt), ctypes.byref(res._h),
-                                       ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(self.device, _lib.CombineStats(),
+                            lambda h, raw, st: lib.sdfhip_scene_combine(self._h, other._h, int(op), ctypes.byref(opt), h, raw, st), want_octdata, want_stats)
 
     def Place(self, rotation, scale, translation, depth=None, want_octdata=False, want_stats=False):
         """Placement (sdfhip_scene_place): this scene resampled under p = scale * rotation @ x + translation -- rotation (3, 3)
@@ -272,21 +242,9 @@ class Scene:
         breadth-first order on the same device; this one is left as it was.  depth: None = this tree's depth, else 0..12.  Nothing is
         pruned (chain Prune), and the identity is a resampling, not a clone.  want_octdata: also the result's host arrays;
         want_stats: a PlaceStats."""
-        from .octdata import OctData
         pl = _lib.Placement(np.asarray(rotation, dtype=np.float32).reshape(3, 3).tolist(), scale, np.asarray(translation, dtype=np.float32).reshape(3).tolist(), depth)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = self.device
-        raw = _lib.COctData()
-        st = _lib.PlaceStats()
-        check(lib.sdfhip_scene_place(self._h, ctypes.byref(pl), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(self.device, _lib.PlaceStats(), lambda h, raw, st: lib.sdfhip_scene_place(self._h, ctypes.byref(pl), h, raw, st),
+                            want_octdata, want_stats)
 
     @staticmethod
     def Compose(parts, depth=None, want_octdata=False, want_stats=False):
@@ -299,7 +257,6 @@ class Scene:
         the largest depth among the parts' scenes, else 0..12.  Nothing is pruned (chain Prune); every source is left as it was.
         Returns what Place returns; want_stats: a ComposeStats.  Raises ValueError on an empty list and on a part that is not such a
         tuple."""
-        from .octdata import OctData
         parts = list(parts)
         if not parts:
             raise ValueError("Compose: no parts")
@@ -318,20 +275,8 @@ class Scene:
                                        np.asarray(t, dtype=np.float32).reshape(3).tolist()))
         arr = (_lib.Instance * len(items))(*items)
         opt = _lib.ComposeOptions(depth)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = parts[0][0].device
-        raw = _lib.COctData()
-        st = _lib.ComposeStats()
-        check(lib.sdfhip_scene_compose(arr, len(items), ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None,
-                                       ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(parts[0][0].device, _lib.ComposeStats(),
+                            lambda h, raw, st: lib.sdfhip_scene_compose(arr, len(items), ctypes.byref(opt), h, raw, st), want_octdata, want_stats)
 
     # -- volumes in and out (sdfhip_volume_build / sdfhip_scene_volume): a dense lattice of distances as a scene and back -------------
     @classmethod
@@ -345,7 +290,6 @@ class Scene:
         spacing.  The value is the trilinear interpolant, continued outside the grid's box at slope 1; the split rule assumes a
         distance, so a truncated field splits everywhere below its truncation: chain Prune.  A non-finite sample is refused
         (ERR_ARG).  want_octdata: also the result's host arrays; want_stats: a VolumeStats."""
-        from .octdata import OctData
         dtypes = {"float32": _lib.VOLUME_F32, "float16": _lib.VOLUME_F16}
         on_device = hasattr(grid, "data_ptr") and hasattr(grid, "is_cuda")
         if on_device:
@@ -380,25 +324,13 @@ class Scene:
         if not 0 <= int(depth) <= 12:
             raise ValueError("FromVolume: depth outside 0..12")
         vol = _lib.Volume((nx, ny, nz), origin, spacing, value_scale, dtypes[name], depth)
-        self = cls.__new__(cls)
-        self._h = ctypes.c_void_p()
-        self.device = int(device)
-        raw = _lib.COctData()
-        st = _lib.VolumeStats()
         if on_device:
-            torch.cuda.current_stream(self.device).synchronize()
-            check(lib.sdfhip_volume_build_device(self.device, ctypes.c_void_p(grid.data_ptr()), ctypes.byref(vol), ctypes.byref(self._h),
-                                                 ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
+            torch.cuda.current_stream(int(device)).synchronize()
+            build, where = lib.sdfhip_volume_build_device, ctypes.c_void_p(grid.data_ptr())
         else:
-            check(lib.sdfhip_volume_build(self.device, grid.ctypes.data, ctypes.byref(vol), ctypes.byref(self._h),
-                                          ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        self._describe()
-        out = [self]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+            build, where = lib.sdfhip_volume_build, grid.ctypes.data
+        return cls._built(device, _lib.VolumeStats(), lambda h, raw, st: build(int(device), where, ctypes.byref(vol), h, raw, st),
+                          want_octdata, want_stats)
 
     def Volume(self, shape, origin=(0, 0, 0), spacing=None, dtype=np.float32, out=None):
         """This scene's distances on a regular lattice (sdfhip_scene_volume[_device]): element (k, j, i) of the (nz, ny, nx) = `shape`
@@ -457,21 +389,9 @@ class Scene:
                                                ctypes.c_void_p(int(stream)) if stream else None))
 
     def _offset(self, mode, amount, depth, level, want_octdata, want_stats):
-        from .octdata import OctData
         opt = _lib.OffsetOptions(mode, amount, depth, level)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = self.device
-        raw = _lib.COctData()
-        st = _lib.OffsetStats()
-        check(lib.sdfhip_scene_offset(self._h, ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(self.device, _lib.OffsetStats(), lambda h, raw, st: lib.sdfhip_scene_offset(self._h, ctypes.byref(opt), h, raw, st),
+                            want_octdata, want_stats)
 
     def Offset(self, delta, depth=None, level=-1, want_octdata=False, want_stats=False):
         """Offset (sdfhip_scene_offset, OFFSET_GROW): this scene's solid grown by `delta` (shrunk when it is negative) -- the tree of
@@ -494,22 +414,9 @@ class Scene:
         meet, the hard operation at 0 -- as a NEW Scene in breadth-first order; both inputs are left as they were.  BLEND_MORPH takes
         `radius` as t (Morph).  depth: None = the deeper of the two trees' depths, else 0..12; level, other_level: each surface's
         level, as Mesh.  Nothing is pruned (chain Prune).  want_octdata: also the result's host arrays; want_stats: a BlendStats."""
-        from .octdata import OctData
         opt = _lib.BlendOptions(op, radius, depth, level, other_level)
-        res = Scene.__new__(Scene)
-        res._h = ctypes.c_void_p()
-        res.device = self.device
-        raw = _lib.COctData()
-        st = _lib.BlendStats()
-        check(lib.sdfhip_scene_blend(self._h, other._h, ctypes.byref(opt), ctypes.byref(res._h), ctypes.byref(raw) if want_octdata else None,
-                                     ctypes.byref(st)))
-        res._describe()
-        out = [res]
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(self.device, _lib.BlendStats(), lambda h, raw, st: lib.sdfhip_scene_blend(self._h, other._h, ctypes.byref(opt), h, raw, st),
+                            want_octdata, want_stats)
 
     def Morph(self, other, t, depth=None, level=-1, other_level=-1, want_octdata=False, want_stats=False):
         """Morph (sdfhip_scene_blend, BLEND_MORPH): the in-between of this scene and `other` -- the tree of a + (b - a) * t, 0 <= t <= 1:
@@ -869,23 +776,8 @@ class TriMesh:
 
     def Build(self, depth, device=0, want_octdata=False, want_scene=True, want_stats=False):
         """The mesh's exact signed distance field as a Scene on `device` (the tree never leaves HBM), and / or its host arrays."""
-        from .octdata import OctData
-        scene = Scene.__new__(Scene)
-        scene._h = ctypes.c_void_p()
-        scene.device = int(device)
-        raw = _lib.COctData()
-        st = _lib.TriMeshStats()
-        check(lib.sdfhip_trimesh_build(int(device), ctypes.byref(self._raw), int(depth), ctypes.byref(scene._h) if want_scene else None,
-                                       ctypes.byref(raw) if want_octdata else None, ctypes.byref(st)))
-        out = []
-        if want_scene:
-            scene._describe()
-            out.append(scene)
-        if want_octdata:
-            out.append(OctData._from_native(raw))
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return Scene._built(device, _lib.TriMeshStats(), lambda h, raw, st: lib.sdfhip_trimesh_build(int(device), ctypes.byref(self._raw), int(depth), h, raw, st),
+                            want_octdata, want_stats, want_scene)
 
     def close(self):
         if self._raw.records:
