@@ -247,9 +247,18 @@ public:
     };
     void Compose(const std::vector<Part> &parts, int depth = -1, sdfhip_compose_stats *stats = nullptr, sdfhip_octdata *host_out = nullptr)
     {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "Compose");
+        const sdfhip_compose_options opt = { (uint32_t)sizeof(sdfhip_compose_options), depth };
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_compose(list.data(), (uint32_t)list.size(), &opt, &fresh, host_out, stats));
+        Adopt(fresh);
+    }
+    // The parts as the C list (Compose, DrawParts, PickParts, SampleParts)
+    static std::vector<sdfhip_instance> InstanceList(const std::vector<Part> &parts, const char *what)
+    {
         std::vector<sdfhip_instance> list(parts.size());
         for (size_t k = 0; k < parts.size(); k++) {
-            if (!parts[k].program || !parts[k].program->scene) throw Error(SDFHIP_ERR_ARG, "Compose: a part has no model loaded");
+            if (!parts[k].program || !parts[k].program->scene) throw Error(SDFHIP_ERR_ARG, std::string(what) + ": a part has no model loaded");
             sdfhip_instance &in = list[k];
             in.scene = parts[k].program->scene;
             in.op = parts[k].op;
@@ -259,10 +268,37 @@ public:
             }
             in.scale = parts[k].scale;
         }
-        const sdfhip_compose_options opt = { (uint32_t)sizeof(sdfhip_compose_options), depth };
-        sdfhip_scene *fresh = nullptr;
-        Check(sdfhip_scene_compose(list.data(), (uint32_t)list.size(), &opt, &fresh, host_out, stats));
-        Adopt(fresh);
+        return list;
+    }
+    // An assembly drawn, probed and picked without baking (sdfhip_instances_render / _pick / _sample; nothing in the reference
+    // corresponds): the parts Compose takes, consumed as they are -- Compose's fold evaluated at every marched point, no tree built,
+    // no Program's model replaced -- so a part can move from one frame to the next at no cost, and every answer names the part it
+    // came from (sdfhip_part_hit.instance, sdfhip_part_probe.instance: the index in `parts`).  DrawParts: a width x height RGBA32F
+    // frame, row 0 at the top; PickParts: the part under pixels {x, y} of the camera `state`; SampleParts: value, part and gradient
+    // at points (xyz: 3 floats per point).  opt (may be null): max_steps, normal_step, SDFHIP_INSTANCES_NO_SKIP
+    static std::vector<float> DrawParts(const std::vector<Part> &parts, const Info &state, uint32_t width, uint32_t height,
+                                        const sdfhip_instances_options *opt = nullptr)
+    {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "DrawParts");
+        std::vector<float> rgba((size_t)width * height * 4);
+        Check(sdfhip_instances_render(list.data(), (uint32_t)list.size(), opt, &state, width, height, rgba.data()));
+        return rgba;
+    }
+    static std::vector<sdfhip_part_hit> PickParts(const std::vector<Part> &parts, const Info &state, const std::vector<uint32_t> &pixels_xy,
+                                                  const sdfhip_instances_options *opt = nullptr)
+    {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "PickParts");
+        std::vector<sdfhip_part_hit> out(pixels_xy.size() / 2);
+        Check(sdfhip_instances_pick(list.data(), (uint32_t)list.size(), opt, &state, pixels_xy.data(), (uint32_t)out.size(), out.data()));
+        return out;
+    }
+    static std::vector<sdfhip_part_probe> SampleParts(const std::vector<Part> &parts, const std::vector<float> &xyz,
+                                                      const sdfhip_instances_options *opt = nullptr)
+    {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "SampleParts");
+        std::vector<sdfhip_part_probe> out(xyz.size() / 3);
+        Check(sdfhip_instances_sample(list.data(), (uint32_t)list.size(), opt, xyz.data(), (uint32_t)out.size(), out.data()));
+        return out;
     }
     // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
     // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at

@@ -833,6 +833,102 @@ SDFHIP_API int sdfhip_scene_raycast_device(sdfhip_scene *scene, const sdfhip_ray
 SDFHIP_API int sdfhip_scene_pick(sdfhip_scene *scene, const sdfhip_info *info, const uint32_t *pixels_xy, uint32_t n, uint32_t max_steps,
                                  sdfhip_hit *out);
 
+/* ---- an assembly of placed instances, drawn, probed and picked without baking ---------------------------
+ * Replaces: nothing in the reference's code -- its shader marches one immutable tree.  sdfhip_scene_compose bakes a list of placed
+ * instances into one tree, which is right once an arrangement has settled and wrong while a part is still being moved: every change
+ * of a placement costs the rebuild before the first frame, and the baked tree has forgotten which part a surface point came from.
+ * The calls below take the SAME list sdfhip_scene_compose takes (1..4096 instances on one device, instance 0 a union; rotation,
+ * scale, translation as sdfhip_placement's) and consume its field directly: nothing is built, nothing is kept on the handles, and
+ * every answer names the instance it came from.  The rule, pinned (fp32, each operation rounded on its own in the order written, the
+ * shader's fused operations fused as DESIGN.md section 3 has them):
+ *   F(p)       sdfhip_scene_compose's fold, word for word: u_k(p) = sdfhip_scene_place's value of instances[k]; v = u_0; then in list
+ *              order UNION v = fminf(v, u_k); INTERSECT v = fmaxf(v, u_k); SUBTRACT v = fmaxf(v, -u_k).  Every look-up starts at its
+ *              source's root: no cursor is carried from step to step, F depends on the point alone
+ *   w(p)       the winner, tracked beside the fold: w = 0; UNION: w = k iff u_k < v before the fold; INTERSECT: iff u_k > v; SUBTRACT:
+ *              iff -u_k > v.  Ties keep the earlier instance
+ *   G(p)       with h = normal_step: (F(p + (h,0,0)) - F(p - (h,0,0)), F(p + (0,h,0)) - F(p - (0,h,0)), F(p + (0,0,h)) - F(p - (0,0,h))),
+ *              the offsets added and subtracted as vectors.  One rule for every op and cursor form, used wherever the shader uses
+ *              gradient(); not normalised (d F / d world = G / (2 h))
+ *   sample     per point: F(p), w(p), G(p)
+ *   raycast    per ray: sdfhip_scene_raycast's march with find + interpol_world replaced by F:
+ *                  prox = 1; i = 0; t = 0; w = 0
+ *                  while ((prox > margin * 2.0f || prox < 0.0f) && i < max_steps) {
+ *                      if (dot(pos, pos) > limit) -> SDFHIP_QUERY_ESCAPED
+ *                      prox = F(pos); w = w(pos); pos = fma(dir, prox, pos); t = t + prox; i++ }
+ *                  -> SDFHIP_QUERY_HIT if !(prox > margin * 2.0f || prox < 0.0f), else SDFHIP_QUERY_EXHAUSTED
+ *              normal = G(position) * (1 / sqrtf(dot(G, G))) for HIT and EXHAUSTED, else 0; instance = the winner of the last
+ *              evaluation (0 when no step was taken): the part under the cursor
+ *   pick       per pixel of a camera block: that march from info->position along the kernel's own ray() (Compute.hlsl:163-168), with
+ *              info's margin and limit
+ *   render     a width x height RGBA32F frame, tightly packed, row 0 at the top, alpha = the march's steps, as sdfhip_render has it:
+ *              every pixel is main() of Compute.hlsl:180-231 line for line (oracle/sdf_oracle.c o_pixel) with find + interpol_world
+ *              replaced by F, gradient() by G -- at the shading point and inside the shadow loop's prox < margin test -- and 100 by
+ *              max_steps.  The sky colour, the black pixel, angle, dist, the 40-step shadow loop, its leave-the-unit-cube exit, the
+ *              prox + margin step and the attenuation are the shader's
+ * The exact skip (on by default).  u_k = (D + e) * s with e the distance from the inverse-mapped point to the source's cube, known
+ * before any look-up, and D >= -0.5625 for every tree an upload accepts (csrc/instances_kernels.h has the argument).  b_k =
+ * (-0.5625f + e) * s <= u_k by monotone rounding alone; for k >= 1 a UNION instance is not looked up when b_k > v, a SUBTRACT instance
+ * when -b_k < v; an INTERSECT instance and instance 0 always are.  A skipped instance can neither change v nor win, so the skip
+ * changes no bit of any output; SDFHIP_INSTANCES_NO_SKIP turns it off (tests, A/B).
+ * opt: NULL = defaults; the caller sets size = sizeof(sdfhip_instances_options), and the struct grows like sdfhip_placement.
+ * max_steps: 0 = 100 (the shader's), else 1..4096.  normal_step: 0 = 2^-10, else finite and above 0.  n = 0 and a 0 x 0 frame are
+ * successes that touch nothing.  A bad ELEMENT -- a non-finite coordinate, a direction that is not finite or is all zero -- is not an
+ * error of the call: it gets SDFHIP_QUERY_INVALID and zeros, and the rest of the batch is answered.
+ *   sdfhip_instances_sample / _raycast / _pick / _render    host arrays, synchronous, on a stream of the call's own
+ *   sdfhip_instances_sample_device / _raycast_device / _render_device
+ *              device pointers on the instances' device; the kernel is enqueued on `stream` (NULL = the HIP default stream), so it
+ *              orders after the caller's earlier work there, and the call synchronises `stream` before it returns and releases the
+ *              per-call instance table.  A fully asynchronous form, and an assembly object that keeps its table resident, do not exist
+ * Every source is untouched and may be freed as soon as the call returns.  Each distinct source is read once, under its own lock,
+ * as sdfhip_scene_compose reads it; each look-up takes its source's own cursor form, and all forms give the same bytes.
+ * SDFHIP_ERR_ARG: a null list, n_instances outside 1..4096, a size the growth rule refuses, unknown flags, max_steps above 4096, a
+ * normal_step that is not finite or is below 0, a non-finite margin or limit, a null info, a frame side above 16384, a null array
+ * with n > 0, and for an instance -- the message names its index -- what sdfhip_scene_compose refuses of it, word for word (a null
+ * scene, an unknown op, a first op other than SDFHIP_COMBINE_UNION, a non-finite field, s <= 0, a rotation that is not orthogonal, a
+ * source on another device than instance 0's); SDFHIP_ERR_NOMEM: out of device memory (nothing leaks); SDFHIP_ERR_DEVICE as elsewhere.
+ * Work is proportional to points x steps x instances looked up.  Measured on an MI355X (profiles/instances_bench.json, DESIGN.md
+ * N17), a 1920 x 1080 frame of 2 / 8 / 32 instances of a 28 M-node scene and a 39 k-node torus: 0.75 / 4.04 / 15.9 ms with the skip,
+ * 0.71 / 4.21 / 21.1 ms without, against 2.80 / 8.03 / 13.6 ms for sdfhip_scene_compose to depth 9 plus one frame of the result (a
+ * resident frame of which takes 0.14 .. 0.31 ms: bake once the arrangement has settled); a pick of one pixel 0.40 .. 0.70 ms. */
+enum { SDFHIP_INSTANCES_NO_SKIP = 1 };   /* sdfhip_instances_options.flags: look every instance up at every point */
+typedef struct sdfhip_instances_options {
+    uint32_t size, flags;           /* sizeof(sdfhip_instances_options) of the caller's header; SDFHIP_INSTANCES_* */
+    uint32_t max_steps;             /* 0 = 100, else 1..4096 */
+    float normal_step;              /* h of G: 0 = 2^-10, else finite and above 0 */
+} sdfhip_instances_options;         /* 16 bytes */
+typedef struct sdfhip_part_probe {  /* 32 bytes: the answer for one point */
+    float value;                    /* F(p) */
+    uint32_t instance;              /* w(p) */
+    uint32_t status;                /* SDFHIP_QUERY_HIT or SDFHIP_QUERY_INVALID */
+    uint32_t pad0_;
+    float gradient[3];              /* G(p), not normalised */
+    uint32_t pad1_;
+} sdfhip_part_probe;
+typedef struct sdfhip_part_hit {    /* 48 bytes: where one ray's march through the assembly ended */
+    float position[3];              /* pos when the loop ended (after the last step) */
+    float t;                        /* the steps' distances summed in fp32 in march order */
+    float normal[3];                /* HIT / EXHAUSTED: G(position) * (1 / sqrtf(dot(G, G))); else 0 */
+    float prox;                     /* the last value read (1.0f if no step was taken) */
+    uint32_t status, steps;
+    uint32_t instance;              /* the winner of the last evaluation: the part under the cursor */
+    uint32_t pad_;
+} sdfhip_part_hit;
+SDFHIP_API int sdfhip_instances_sample(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                       const float *xyz, uint32_t n, sdfhip_part_probe *out);
+SDFHIP_API int sdfhip_instances_sample_device(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                              const float *d_xyz, uint32_t n, sdfhip_part_probe *d_out, void *stream);
+SDFHIP_API int sdfhip_instances_raycast(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                        const sdfhip_ray *rays, uint32_t n, float margin, float limit, sdfhip_part_hit *out);
+SDFHIP_API int sdfhip_instances_raycast_device(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                               const sdfhip_ray *d_rays, uint32_t n, float margin, float limit, sdfhip_part_hit *d_out,
+                                               void *stream);
+SDFHIP_API int sdfhip_instances_pick(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                     const sdfhip_info *info, const uint32_t *pixels_xy, uint32_t n, sdfhip_part_hit *out);
+SDFHIP_API int sdfhip_instances_render(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                       const sdfhip_info *info, uint32_t width, uint32_t height, float *rgba);
+SDFHIP_API int sdfhip_instances_render_device(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_instances_options *opt,
+                                              const sdfhip_info *info, uint32_t width, uint32_t height, float *d_rgba, void *stream);
+
 /* ---- surface extraction: a resident scene as triangles ------------------------------------------------
  * Replaces: nothing in the reference's code -- its tree only ever becomes pixels.  A scene that was built, carved and picked here
  * leaves as geometry: a triangle soup of 3 * n_triangles vertices of six floats {position, normal}, the layout of sdfhip_points.data,

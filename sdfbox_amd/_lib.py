@@ -49,12 +49,13 @@ OFFSET_GROW, OFFSET_SHELL = 0, 1     # sdfhip_scene_offset: dist - amount / fabs
 BLEND_UNION, BLEND_INTERSECT, BLEND_SUBTRACT, BLEND_MORPH = 0, 1, 2, 3      # sdfhip_scene_blend: smooth A or B, A and B, A without B; the in-between
 VOLUME_F32, VOLUME_F16 = 0, 1        # sdfhip_volume.dtype
 QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdfhip_probe.status / sdfhip_hit.status
+INSTANCES_NO_SKIP = 1                # sdfhip_instances_options.flags: look every instance up at every point
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -348,6 +349,31 @@ else:
     assert (ctypes.sizeof(Probe), ctypes.sizeof(Ray), ctypes.sizeof(Hit)) == (32, 32, 48)
 
 
+    class InstancesOptions(ctypes.Structure):
+        """sdfhip_instances_options: flags INSTANCES_NO_SKIP or 0; max_steps None = 100 (the shader's), else 1..4096; normal_step None =
+        2^-10, else finite and above 0."""
+        _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("max_steps", ctypes.c_uint32), ("normal_step", ctypes.c_float)]
+
+        def __init__(self, flags=0, max_steps=None, normal_step=None):
+            super().__init__(ctypes.sizeof(type(self)), int(flags), 0 if max_steps is None else int(max_steps),
+                             0.0 if normal_step is None else float(normal_step))
+
+
+    class PartProbe(ctypes.Structure):
+        """sdfhip_part_probe: the answer for one point of sdfhip_instances_sample."""
+        _fields_ = [("value", ctypes.c_float), ("instance", ctypes.c_uint32), ("status", ctypes.c_uint32), ("pad0_", ctypes.c_uint32),
+                    ("gradient", ctypes.c_float * 3), ("pad1_", ctypes.c_uint32)]
+
+
+    class PartHit(ctypes.Structure):
+        """sdfhip_part_hit: where one ray's march through an assembly ended (sdfhip_instances_raycast, sdfhip_instances_pick)."""
+        _fields_ = [("position", ctypes.c_float * 3), ("t", ctypes.c_float), ("normal", ctypes.c_float * 3), ("prox", ctypes.c_float),
+                    ("status", ctypes.c_uint32), ("steps", ctypes.c_uint32), ("instance", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+    assert (ctypes.sizeof(InstancesOptions), ctypes.sizeof(PartProbe), ctypes.sizeof(PartHit)) == (16, 32, 48)
+
+
     class MeshOptions(ctypes.Structure):
         """sdfhip_mesh_options: level -1 = the leaves (full detail), 0..12 = the level-of-detail mesh of that level."""
         _fields_ = [("size", ctypes.c_uint32), ("level", ctypes.c_int32)]
@@ -513,6 +539,15 @@ _SIG = {
     "sdfhip_scene_raycast": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp]),
     "sdfhip_scene_raycast_device": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_float, _c.c_float, _c.c_uint32, _vp, _vp]),
     "sdfhip_scene_pick": (_c.c_int, [_vp, _c.POINTER(Info), _vp, _c.c_uint32, _c.c_uint32, _vp]),
+    "sdfhip_instances_sample": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _vp, _c.c_uint32, _vp]),
+    "sdfhip_instances_sample_device": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _vp, _c.c_uint32, _vp, _vp]),
+    "sdfhip_instances_raycast": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _vp, _c.c_uint32, _c.c_float, _c.c_float, _vp]),
+    "sdfhip_instances_raycast_device": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _vp, _c.c_uint32, _c.c_float, _c.c_float,
+                                                   _vp, _vp]),
+    "sdfhip_instances_pick": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _c.POINTER(Info), _vp, _c.c_uint32, _vp]),
+    "sdfhip_instances_render": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _c.POINTER(Info), _c.c_uint32, _c.c_uint32, _vp]),
+    "sdfhip_instances_render_device": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(InstancesOptions), _c.POINTER(Info), _c.c_uint32, _c.c_uint32,
+                                                  _vp, _vp]),
     "sdfhip_mesh_options_default": (None, [_c.POINTER(MeshOptions)]),
     "sdfhip_scene_mesh": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _c.POINTER(CMesh), _c.POINTER(MeshStats)]),
     "sdfhip_scene_mesh_device": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp]),

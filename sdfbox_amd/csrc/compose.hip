@@ -15,7 +15,7 @@
 // k_place_level.  Each distinct source is read once, under its own lock, one after the other.  The call runs on a stream of its own
 // with memory of its own; nothing is kept on the handles.
 #include "compose_kernels.h"
-#include "level_build.h"      // host_support.h; Source, read_source, build_levels
+#include "compose_host.h"     // check_instance, read_instance (shared with instances.hip); level_build.h: Source, build_levels
 #include "abi_guard.h"
 
 #include <algorithm>
@@ -34,33 +34,12 @@ static_assert(SDFHIP_COMBINE_UNION == COMPOSE_UNION && SDFHIP_COMBINE_INTERSECT 
 static_assert(FORM_GENERIC == COMPOSE_FORM_GENERIC && FORM_GRID == COMPOSE_FORM_GRID && FORM_SPLIT == COMPOSE_FORM_SPLIT,
               "compose_kernels.h restates level_build.h's forms");
 
-namespace {
-
-constexpr uint32_t COMPOSE_MAX_INSTANCES = 4096;
-
-// what the header refuses of instance k, before any device call: the op, the placement's checks (check_similarity), the handle
-int check_instance(const sdfhip_instance *in, uint32_t k)
-{
-    if (in->op < SDFHIP_COMBINE_UNION || in->op > SDFHIP_COMBINE_SUBTRACT) return fail(SDFHIP_ERR_ARG, "scene_compose: instance %u: unknown op %d", k, in->op);
-    if (k == 0 && in->op != SDFHIP_COMBINE_UNION)
-        return fail(SDFHIP_ERR_ARG, "scene_compose: instance 0: op %d, but the first instance has nothing to join: SDFHIP_COMBINE_UNION", in->op);
-    char what[48];
-    snprintf(what, sizeof what, "scene_compose: instance %u", k);
-    if (const int rc = check_similarity(what, in->rotation, in->scale, in->translation)) return rc;
-    if (!in->scene) return fail(SDFHIP_ERR_ARG, "scene_compose: instance %u: null scene", k);
-    return SDFHIP_OK;
-}
-
-}  // namespace
-
 extern "C" int sdfhip_scene_compose(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_compose_options *opt, sdfhip_scene **out,
                                     sdfhip_octdata *host_out, sdfhip_compose_stats *stats)
 try {
     const auto t0 = std::chrono::steady_clock::now();
     if (out) *out = nullptr;
-    if (!instances) return fail(SDFHIP_ERR_ARG, "scene_compose: null instance list");
-    if (n_instances < 1 || n_instances > COMPOSE_MAX_INSTANCES)
-        return fail(SDFHIP_ERR_ARG, "scene_compose: %u instances: 1..%u", n_instances, COMPOSE_MAX_INSTANCES);
+    if (const int rc = check_instance_count("scene_compose", instances, n_instances)) return rc;
     if (!out && !host_out) return fail(SDFHIP_ERR_ARG, "scene_compose: both outputs are null");
     int depth_opt = -1;
     if (opt) {
@@ -70,38 +49,24 @@ try {
         depth_opt = opt->depth;
     }
     for (uint32_t k = 0; k < n_instances; k++)
-        if (const int rc = check_instance(instances + k, k)) return rc;
+        if (const int rc = check_instance("scene_compose", instances + k, k)) return rc;
 
     // What the call uses of each distinct handle is read under that handle's lock, one handle after the other and never two locks
     // at once, and the lock is released before any work is issued, as sdfhip_scene_place does: the records are only ever read.
-    std::vector<std::pair<const sdfhip_scene *, Source>> sources;
+    InstanceSources sources;
     std::vector<ComposeInstance> table(n_instances);          // (before `call`: alive until the stream that copies it is drained)
     uint64_t nodes_sum = 0;
     uint32_t deepest = 0;
     for (uint32_t k = 0; k < n_instances; k++) {
-        const sdfhip_instance &in = instances[k];
-        auto at = std::find_if(sources.begin(), sources.end(), [&](const auto &s) { return s.first == in.scene; });
-        if (at == sources.end()) {
-            sources.emplace_back(in.scene, read_source(in.scene));
-            at = sources.end() - 1;
-            nodes_sum += at->second.Q.n_nodes;
-        }
-        const Source &src = at->second;
-        if (src.device != sources.front().second.device)
-            return fail(SDFHIP_ERR_ARG, "scene_compose: instance %u lives on device %d, instance 0 on device %d: one device", k, src.device,
-                        sources.front().second.device);
-        if (depth_opt < 0 && src.depth > (uint32_t)TREE_MAX_DEPTH)
+        const Source *src = nullptr;
+        bool fresh = false;
+        if (const int rc = read_instance("scene_compose", sources, instances[k], k, table[k], &src, &fresh)) return rc;
+        if (fresh) nodes_sum += src->Q.n_nodes;
+        if (depth_opt < 0 && src->depth > (uint32_t)TREE_MAX_DEPTH)
             return fail(SDFHIP_ERR_BAD_TREE,
                         "scene_compose: instance %u: the source is not a consistent tree of at most %d levels, so it has no depth to take: give one", k,
                         TREE_MAX_DEPTH);
-        deepest = std::max(deepest, src.depth);
-        ComposeInstance &I = table[k];
-        I.Q = src.Q;
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) I.M.r[i][j] = in.rotation[i][j];
-        I.M.s = in.scale; I.M.inv = 1.0f / in.scale;
-        I.M.tx = in.translation[0]; I.M.ty = in.translation[1]; I.M.tz = in.translation[2];
-        I.op = in.op; I.form = (int32_t)src.form;
+        deepest = std::max(deepest, src->depth);
     }
     const int depth = depth_opt < 0 ? (int)deepest : depth_opt;
     const int device = sources.front().second.device;

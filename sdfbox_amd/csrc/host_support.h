@@ -8,6 +8,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstring>
 #include <thread>
 #include <vector>
 
@@ -29,6 +31,25 @@ inline void cpu_relax() { __builtin_ia32_pause(); }      // inside a spin loop
 #else
 inline void cpu_relax() { std::this_thread::yield(); }
 #endif
+
+// The camera block as a march reads it: render.hip's unpack_info, field for field (the same IEEE operations, once per call on the
+// host), for the translation units outside the renderer's measured sources (query.hip, instances.hip)
+inline void unpack_camera(const sdfhip_info *in, FrameInfo &I)
+{
+    memset(&I, 0, sizeof I);
+    I.h0x = in->heading[0][0]; I.h0y = in->heading[0][1]; I.h0z = in->heading[0][2];
+    I.h1x = in->heading[1][0]; I.h1y = in->heading[1][1]; I.h1z = in->heading[1][2];
+    I.h2x = in->heading[2][0]; I.h2y = in->heading[2][1]; I.h2z = in->heading[2][2];
+    I.posx = in->position[0]; I.posy = in->position[1]; I.posz = in->position[2];
+    I.margin = in->margin;
+    I.margin2 = in->margin * 2.0f;
+    I.screen_w = in->screen_size[0]; I.screen_h = in->screen_size[1];
+    I.limit = in->limit;
+    I.lightx = in->light[0]; I.lighty = in->light[1]; I.lightz = in->light[2];
+    I.fov = in->fov;
+    I.k_strength = exp2f(in->strength) - 1.0f;
+    I.half_aspect = in->screen_size[0] / in->screen_size[1] * 0.5f;
+}
 
 // A buffer on the current device that grows on demand; its owner keeps the pointer and the capacity in bytes.
 // grow_buffer: room for `need` bytes (the contents are not kept).  drain: a stream whose work may still use the old block, waited

@@ -57,22 +57,6 @@ QueryScene scene_of(const sdfhip_scene *s)
     return QueryScene{s->nodes, s->n, s->d_top, s->d_fine, s->top_level, s->fine_bits};
 }
 
-// render.hip's unpack_info, the fields a primary march reads (the same IEEE operations, once per call on the host)
-void unpack_camera(const sdfhip_info *in, FrameInfo &I)
-{
-    memset(&I, 0, sizeof I);
-    I.h0x = in->heading[0][0]; I.h0y = in->heading[0][1]; I.h0z = in->heading[0][2];
-    I.h1x = in->heading[1][0]; I.h1y = in->heading[1][1]; I.h1z = in->heading[1][2];
-    I.h2x = in->heading[2][0]; I.h2y = in->heading[2][1]; I.h2z = in->heading[2][2];
-    I.posx = in->position[0]; I.posy = in->position[1]; I.posz = in->position[2];
-    I.margin = in->margin;
-    I.margin2 = in->margin * 2.0f;
-    I.screen_w = in->screen_size[0]; I.screen_h = in->screen_size[1];
-    I.limit = in->limit;
-    I.fov = in->fov;
-    I.half_aspect = in->screen_size[0] / in->screen_size[1] * 0.5f;
-}
-
 dim3 blocks_of(uint32_t n) { return dim3((n + QUERY_THREADS - 1) / QUERY_THREADS); }
 
 template <class CursorT>

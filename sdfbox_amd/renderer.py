@@ -257,26 +257,121 @@ class Scene:
         the largest depth among the parts' scenes, else 0..12.  Nothing is pruned (chain Prune); every source is left as it was.
         Returns what Place returns; want_stats: a ComposeStats.  Raises ValueError on an empty list and on a part that is not such a
         tuple."""
+        parts, arr = Scene._instances("Compose", parts)
+        opt = _lib.ComposeOptions(depth)
+        return Scene._built(parts[0][0].device, _lib.ComposeStats(),
+                            lambda h, raw, st: lib.sdfhip_scene_compose(arr, len(arr), ctypes.byref(opt), h, raw, st), want_octdata, want_stats)
+
+    @staticmethod
+    def _instances(what, parts):
+        """(the parts as a list, the sdfhip_instance array) of a list of (scene, (R, s, t)) or (scene, (R, s, t), op); ValueError on an
+        empty list and on a part that is not such a tuple.  what: the method's name for the messages."""
         parts = list(parts)
         if not parts:
-            raise ValueError("Compose: no parts")
+            raise ValueError(f"{what}: no parts")
         items = []
         for k, part in enumerate(parts):
             if not isinstance(part, (tuple, list)) or len(part) not in (2, 3):
-                raise ValueError(f"Compose: part {k} is neither (scene, (R, s, t)) nor (scene, (R, s, t), op)")
+                raise ValueError(f"{what}: part {k} is neither (scene, (R, s, t)) nor (scene, (R, s, t), op)")
             scene, pl = part[0], part[1]
             if not isinstance(scene, Scene):
-                raise ValueError(f"Compose: part {k}: not a Scene")
+                raise ValueError(f"{what}: part {k}: not a Scene")
             if not isinstance(pl, (tuple, list)) or len(pl) != 3:
-                raise ValueError(f"Compose: part {k}: the placement is not (R, s, t)")
+                raise ValueError(f"{what}: part {k}: the placement is not (R, s, t)")
             R, sc, t = pl
             op = _lib.COMBINE_UNION if len(part) == 2 else int(part[2])
             items.append(_lib.Instance(scene._h, op, np.asarray(R, dtype=np.float32).reshape(3, 3).tolist(), sc,
                                        np.asarray(t, dtype=np.float32).reshape(3).tolist()))
-        arr = (_lib.Instance * len(items))(*items)
-        opt = _lib.ComposeOptions(depth)
-        return Scene._built(parts[0][0].device, _lib.ComposeStats(),
-                            lambda h, raw, st: lib.sdfhip_scene_compose(arr, len(items), ctypes.byref(opt), h, raw, st), want_octdata, want_stats)
+        return parts, (_lib.Instance * len(items))(*items)
+
+    # -- an assembly of placed instances, drawn, probed and picked without baking (sdfhip_instances_*) -----------------------------------
+    # parts: what Compose takes.  skip=False looks every instance up at every point (INSTANCES_NO_SKIP: the same bytes, for tests and
+    # the A/B); max_steps None = 100; normal_step None = 2^-10, the h of the six-tap gradient G.
+    @staticmethod
+    def _instances_options(skip, max_steps, normal_step):
+        return _lib.InstancesOptions(0 if skip else _lib.INSTANCES_NO_SKIP, max_steps, normal_step)
+
+    @staticmethod
+    def SampleParts(parts, points, skip=True, normal_step=None):
+        """The assembly's field at points (n, 3) float32 (sdfhip_instances_sample): n sdfhip_part_probe records -- value = Compose's
+        fold F(p) evaluated there, instance = the part that decided it, status, gradient = G(p), not normalised.  A non-finite point
+        gets QUERY_INVALID and zeros.  Nothing is built and nothing is kept."""
+        _, arr = Scene._instances("SampleParts", parts)
+        opt = Scene._instances_options(skip, None, normal_step)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(p), dtype=np.dtype(_lib.PartProbe))
+        check(lib.sdfhip_instances_sample(arr, len(arr), ctypes.byref(opt), p.ctypes.data, len(p), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def RaycastParts(parts, origins, dirs, margin, limit, max_steps=None, skip=True, normal_step=None):
+        """Raycast's march through the assembly's field (sdfhip_instances_raycast): n sdfhip_part_hit records (position, t, normal,
+        prox, status, steps, instance = the part the march ended on)."""
+        _, arr = Scene._instances("RaycastParts", parts)
+        opt = Scene._instances_options(skip, max_steps, normal_step)
+        rays = _rays(origins, dirs)
+        out = np.zeros(len(rays), dtype=np.dtype(_lib.PartHit))
+        check(lib.sdfhip_instances_raycast(arr, len(arr), ctypes.byref(opt), rays.ctypes.data, len(rays), float(margin), float(limit), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def PickParts(parts, state, pixels, max_steps=None, skip=True, normal_step=None):
+        """Which part is under the pixels (n, 2) {x, y} of the camera `state` (a Logic or an Info): RaycastParts from the camera's
+        position along the kernel's own ray() for each pixel, margin and limit the camera's (sdfhip_instances_pick)."""
+        _, arr = Scene._instances("PickParts", parts)
+        opt = Scene._instances_options(skip, max_steps, normal_step)
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1, 2)
+        out = np.zeros(len(px), dtype=np.dtype(_lib.PartHit))
+        info = state if isinstance(state, Info) else state.State
+        check(lib.sdfhip_instances_pick(arr, len(arr), ctypes.byref(opt), ctypes.byref(info), px.ctypes.data, len(px), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def DrawParts(parts, state, width, height, max_steps=None, skip=True, normal_step=None):
+        """A (height, width, 4) float32 frame of the assembly, row 0 at the top, alpha = the march's steps (sdfhip_instances_render):
+        the shader's pixel with Compose's fold in the place of the tree's distance and G in the place of gradient().  No tree is
+        built: a placement may change from one frame to the next at no cost."""
+        _, arr = Scene._instances("DrawParts", parts)
+        opt = Scene._instances_options(skip, max_steps, normal_step)
+        width, height = int(width), int(height)
+        if width < 0 or height < 0:
+            raise ValueError("DrawParts: width and height must not be negative")
+        out = np.zeros((height, width, 4), dtype=np.float32)
+        info = state if isinstance(state, Info) else state.State
+        check(lib.sdfhip_instances_render(arr, len(arr), ctypes.byref(opt), ctypes.byref(info), width, height, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def SamplePartsDevice(parts, xyz_ptr, n, out_ptr, stream=None, skip=True, normal_step=None):
+        """SampleParts for n points (n x 3 floats) in device memory at `xyz_ptr` into n sdfhip_part_probe records at `out_ptr`: enqueued
+        on `stream` (a raw hipStream_t value or None) after the caller's earlier work there; the call waits for that stream."""
+        _, arr = Scene._instances("SamplePartsDevice", parts)
+        opt = Scene._instances_options(skip, None, normal_step)
+        if int(n) < 0:
+            raise ValueError("SamplePartsDevice: n must not be negative")
+        check(lib.sdfhip_instances_sample_device(arr, len(arr), ctypes.byref(opt), ctypes.c_void_p(int(xyz_ptr)), int(n), ctypes.c_void_p(int(out_ptr)),
+                                                 ctypes.c_void_p(int(stream)) if stream else None))
+
+    @staticmethod
+    def RaycastPartsDevice(parts, rays_ptr, n, margin, limit, out_ptr, max_steps=None, stream=None, skip=True, normal_step=None):
+        """RaycastParts for n sdfhip_ray records in device memory into n sdfhip_part_hit records at `out_ptr`, as SamplePartsDevice."""
+        _, arr = Scene._instances("RaycastPartsDevice", parts)
+        opt = Scene._instances_options(skip, max_steps, normal_step)
+        if int(n) < 0:
+            raise ValueError("RaycastPartsDevice: n must not be negative")
+        check(lib.sdfhip_instances_raycast_device(arr, len(arr), ctypes.byref(opt), ctypes.c_void_p(int(rays_ptr)), int(n), float(margin), float(limit),
+                                                  ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(stream)) if stream else None))
+
+    @staticmethod
+    def DrawPartsDevice(parts, state, width, height, out_ptr, max_steps=None, stream=None, skip=True, normal_step=None):
+        """DrawParts into width x height float4 pixels of device memory at `out_ptr`, as SamplePartsDevice."""
+        _, arr = Scene._instances("DrawPartsDevice", parts)
+        opt = Scene._instances_options(skip, max_steps, normal_step)
+        if int(width) < 0 or int(height) < 0:
+            raise ValueError("DrawPartsDevice: width and height must not be negative")
+        info = state if isinstance(state, Info) else state.State
+        check(lib.sdfhip_instances_render_device(arr, len(arr), ctypes.byref(opt), ctypes.byref(info), int(width), int(height),
+                                                 ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(stream)) if stream else None))
 
     # -- volumes in and out (sdfhip_volume_build / sdfhip_scene_volume): a dense lattice of distances as a scene and back -------------
     @classmethod
