@@ -424,6 +424,25 @@ public:
         Check(sdfhip_scene_measure(scene, &opt, &out));
         return out;
     }
+    // Cross-sections (sdfhip_scene_slice; nothing that runs in the reference corresponds -- its Layers.hlsl, a z-slice viewer, is dead
+    // code): the contours of the loaded model in the planes dot(normal, p) = offset + k * pitch, k = 0 .. layers - 1, as directed
+    // segments with the solid on the left seen from the tip of the normal, in the pinned node-major order (each record carries its
+    // layer; std::stable_sort on it groups them).  layer_counts, when given, receives the records per layer.  level: as Mesh()
+    std::vector<sdfhip_segment> Slice(const float (&normal)[3], float offset = 0.5f, float pitch = 0.0f, uint32_t layers = 1, int level = -1,
+                                      std::vector<uint32_t> *layer_counts = nullptr, sdfhip_slice_stats *stats = nullptr)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Slice: no model loaded");
+        sdfhip_slice_options opt;
+        sdfhip_slice_options_default(&opt);
+        opt.level = level;
+        opt.normal[0] = normal[0]; opt.normal[1] = normal[1]; opt.normal[2] = normal[2];
+        opt.offset = offset; opt.pitch = pitch; opt.layers = layers;
+        sdfhip_slice slice = { 0, nullptr, 0, nullptr };
+        Check(sdfhip_scene_slice(scene, &opt, &slice, stats));
+        struct Release { sdfhip_slice &s; ~Release() { sdfhip_slice_free(&s); } } release{ slice };
+        if (layer_counts) layer_counts->assign(slice.layer_counts, slice.layer_counts + slice.layers);
+        return slice.n_segments ? std::vector<sdfhip_segment>(slice.segments, slice.segments + slice.n_segments) : std::vector<sdfhip_segment>();
+    }
     // Triangle mesh -> model (sdfhip_trimesh_prepare + sdfhip_trimesh_build; nothing in the live reference corresponds -- the intent of its
     // abandoned GpuGenerator.cs): verts6 = 3 * n vertices of six floats as Mesh() returns them (normals ignored), counter-clockwise seen
     // from outside; the exact signed distance field becomes the loaded model, placed where the coordinates say (fit = false) or fitted

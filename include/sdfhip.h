@@ -1038,6 +1038,62 @@ typedef struct sdfhip_measure {
 SDFHIP_API void sdfhip_measure_options_default(sdfhip_measure_options *opt);
 SDFHIP_API int sdfhip_scene_measure(sdfhip_scene *scene, const sdfhip_measure_options *opt, sdfhip_measure *out);
 
+/* ---- cross-sections: the contours of a stack of planes ------------------------------------------------
+ * Replaces: nothing that runs in the reference -- its tree only ever becomes pixels (its Layers.hlsl, a z-slice viewer, is dead code).
+ * The outline of the solid in a plane, or in a stack of parallel planes: what a printer's slicer consumes after sdfhip_scene_offset, what
+ * a section view draws and what a fit check between two parts looks at.  The slice is exactly plane x (the triangles of
+ * sdfhip_scene_mesh), made on the device without a triangle ever being written: directed segments of 32 bytes, consistent with
+ * sdfhip_scene_mesh and sdfhip_scene_measure by construction.
+ * The rule, pinned (fp32, each operation rounded on its own in the order written; DESIGN.md section 8 has it with the GPU path):
+ *   triangles  N7's, untouched: the cells of `level`, the six tetrahedra, the table's triangles (p0, p1, p2), counter-clockwise seen from
+ *              outside, their vertices sdfhip_scene_mesh's positions
+ *   height     d_i = ((nx * p_ix) + (ny * p_iy)) + (nz * p_iz) and h_k = offset + (float)k * pitch, k = 0 .. layers - 1 (layers = 1: h_0 =
+ *              offset, whatever the pitch).  The normal is used as given, never normalised: h is in the units of dot(normal, p)
+ *   side       vertex i is above plane k iff d_i >= h_k (these two floats compared, nothing subtracted).  A triangle gives one segment for
+ *              plane k iff its three vertices are not all on one side; a triangle lying in the plane gives none
+ *   point      on a triangle edge whose ends differ in side, ALWAYS from the below end a to the above end b, whichever way the triangle
+ *              walks it: sa = d_a - h_k, sb = d_b - h_k, t = sa / (sa - sb), per axis q = a + (b - a) * t -- two triangles that share an
+ *              edge with the same vertex bits produce the same three words, which is what closed contours rest on
+ *   direction  of the triangle's edges 0->1, 1->2, 2->0 exactly one goes above->below and one below->above: segment.a is the point on the
+ *              former, segment.b the point on the latter.  The solid lies on the left seen from the tip of the normal: outer loops are
+ *              counter-clockwise and holes clockwise in any right-handed basis (u, v, normal)
+ *   zero length  segments are emitted as they fall (a plane through a mesh vertex gives them); they disturb no point's balance
+ *   order      ascending node index, then tetrahedron, then triangle, then layer k ascending; each record carries its layer and its node.
+ *              layer_counts[k] is the number of records of layer k.  Grouping by layer is a stable sort on `layer`, left to the caller
+ * Cells of different depth meet in T-junctions as in the mesh; nothing is welded, patched or chained into loops.
+ *   sdfhip_scene_slice         the records (node-major) and the layers' counts in host memory (release with sdfhip_slice_free),
+ *                              synchronous, on the scene's own stream, under the handle's lock.  layer_counts holds `layers` words on every
+ *                              success; segments is NULL when there is no record
+ *   sdfhip_scene_slice_device  ALWAYS returns the count in *n_segments (one host synchronisation on `stream`); writes the records to
+ *                              d_segments (device memory on the scene's device, 16-byte aligned) only if the count fits
+ *                              capacity_segments -- capacity 0 with a null pointer asks for the count -- asynchronously on `stream` (NULL =
+ *                              the HIP default stream), node-major.  d_layer_counts (layers words of device memory, or NULL) is written
+ *                              whether or not the records fit
+ * opt: NULL = the defaults below; the struct grows like sdfhip_mesh_options.  stats may be NULL.
+ * SDFHIP_ERR_ARG: a null scene, output or count; level outside -1..12; a normal that is not finite or all zero; an offset that is not
+ * finite; layers 0 or above 65 536; a pitch that is not finite, or not > 0 when layers > 1; an options struct the size rules refuse; a
+ * capacity without a buffer, a buffer that is not 16-byte aligned; a result of more than 2^31 - 1 segments.  SDFHIP_ERR_BAD_TREE and
+ * SDFHIP_ERR_NOMEM as sdfhip_scene_mesh (nothing leaks, the scene is untouched).  *out is zeroed on every failure. */
+typedef struct sdfhip_slice_options {
+    uint32_t size; int32_t level;      /* size: set by sdfhip_slice_options_default; level: as sdfhip_mesh_options */
+    float normal[3]; float offset;     /* plane k: dot(normal, p) = h_k */
+    float pitch; uint32_t layers;      /* h_k = offset + (float)k * pitch, k = 0 .. layers-1 */
+} sdfhip_slice_options;
+typedef struct sdfhip_segment { float a[3]; uint32_t layer; float b[3]; uint32_t node; } sdfhip_segment;   /* 32 bytes */
+typedef struct sdfhip_slice { uint32_t n_segments; sdfhip_segment *segments; uint32_t layers; uint32_t *layer_counts; } sdfhip_slice;
+typedef struct sdfhip_slice_stats {
+    uint32_t nodes, cells, cells_cut;  /* as sdfhip_mesh_stats */
+    uint32_t cells_crossed;            /* the cut cells that emit at least one segment */
+    uint32_t n_segments;
+    float kernel_ms;                   /* HIP events around the count, scan and emit kernels */
+    float total_ms;                    /* host clock, the whole call */
+} sdfhip_slice_stats;
+SDFHIP_API void sdfhip_slice_options_default(sdfhip_slice_options *opt);          /* level -1, normal (0,0,1), offset 0.5, pitch 0, layers 1 */
+SDFHIP_API int sdfhip_scene_slice(sdfhip_scene *scene, const sdfhip_slice_options *opt, sdfhip_slice *out, sdfhip_slice_stats *stats);
+SDFHIP_API int sdfhip_scene_slice_device(sdfhip_scene *scene, const sdfhip_slice_options *opt, sdfhip_segment *d_segments, uint32_t capacity_segments,
+                                         uint32_t *d_layer_counts, uint32_t *n_segments, void *stream);
+SDFHIP_API void sdfhip_slice_free(sdfhip_slice *slice);
+
 /* ---- exact distance: clearance query, offset and shell ------------------------------------------------
  * Replaces: nothing in the reference's code -- its field is only ever read as stored, and the stored field is a distance only in a
  * thin band round the surface: a leaf of edge S holds values in [-0.5 S, 1.5 S] and every leaf away from the surface is saturated (the

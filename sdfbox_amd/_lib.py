@@ -55,7 +55,7 @@ INSTANCES_NO_SKIP = 1                # sdfhip_instances_options.flags: look ever
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -435,6 +435,35 @@ else:
     assert (ctypes.sizeof(MeasureOptions), ctypes.sizeof(Measure)) == (8, 216)
 
 
+    class SliceOptions(ctypes.Structure):
+        """sdfhip_slice_options: plane k is dot(normal, p) = offset + k * pitch, k = 0 .. layers - 1 (the normal as given, never
+        normalised); level as MeshOptions."""
+        _fields_ = [("size", ctypes.c_uint32), ("level", ctypes.c_int32), ("normal", ctypes.c_float * 3), ("offset", ctypes.c_float),
+                    ("pitch", ctypes.c_float), ("layers", ctypes.c_uint32)]
+
+        def __init__(self, normal=(0.0, 0.0, 1.0), offset=0.5, pitch=0.0, layers=1, level=-1):
+            super().__init__(ctypes.sizeof(type(self)), int(level), (ctypes.c_float * 3)(*[float(x) for x in normal]), float(offset), float(pitch),
+                             int(layers))
+
+
+    class Segment(ctypes.Structure):
+        """sdfhip_segment: from a to b the solid lies on the left, seen from the tip of the normal"""
+        _fields_ = [("a", ctypes.c_float * 3), ("layer", ctypes.c_uint32), ("b", ctypes.c_float * 3), ("node", ctypes.c_uint32)]
+
+
+    class CSlice(ctypes.Structure):
+        _fields_ = [("n_segments", ctypes.c_uint32), ("segments", ctypes.POINTER(Segment)), ("layers", ctypes.c_uint32),
+                    ("layer_counts", ctypes.POINTER(ctypes.c_uint32))]
+
+
+    class SliceStats(ctypes.Structure):
+        _fields_ = [("nodes", ctypes.c_uint32), ("cells", ctypes.c_uint32), ("cells_cut", ctypes.c_uint32), ("cells_crossed", ctypes.c_uint32),
+                    ("n_segments", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(SliceOptions), ctypes.sizeof(Segment), ctypes.sizeof(CSlice), ctypes.sizeof(SliceStats)) == (32, 32, 32, 28)
+
+
     class TriMeshOptions(ctypes.Structure):
         """sdfhip_trimesh_options: fit 0 = coordinates as given, 1 = bounding box centred at 0.5 with its longest side `fill` (None = default)."""
         _fields_ = [("size", ctypes.c_uint32), ("fit", ctypes.c_int32), ("fill", ctypes.c_float)]
@@ -554,6 +583,10 @@ _SIG = {
     "sdfhip_mesh_free": (None, [_c.POINTER(CMesh)]),
     "sdfhip_measure_options_default": (None, [_c.POINTER(MeasureOptions)]),
     "sdfhip_scene_measure": (_c.c_int, [_vp, _c.POINTER(MeasureOptions), _c.POINTER(Measure)]),
+    "sdfhip_slice_options_default": (None, [_c.POINTER(SliceOptions)]),
+    "sdfhip_scene_slice": (_c.c_int, [_vp, _c.POINTER(SliceOptions), _c.POINTER(CSlice), _c.POINTER(SliceStats)]),
+    "sdfhip_scene_slice_device": (_c.c_int, [_vp, _c.POINTER(SliceOptions), _vp, _c.c_uint32, _vp, _c.POINTER(_c.c_uint32), _vp]),
+    "sdfhip_slice_free": (None, [_c.POINTER(CSlice)]),
     "sdfhip_mesh_save_ply": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
     "sdfhip_mesh_save_obj": (_c.c_int, [_c.POINTER(CMesh), _c.c_char_p]),
     "sdfhip_load_ply_mesh": (_c.c_int, [_c.c_char_p, _c.POINTER(CMesh)]),

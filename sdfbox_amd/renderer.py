@@ -593,6 +593,40 @@ class Scene:
         check(lib.sdfhip_scene_measure(self._h, ctypes.byref(opt), ctypes.byref(out)))
         return out
 
+    # -- cross-sections (sdfhip_scene_slice): the contours of a stack of planes ---------------------------------------------------
+    def Slice(self, normal=(0.0, 0.0, 1.0), offset=0.5, pitch=0.0, layers=1, level=-1, want_stats=True):
+        """The contours of the solid in the planes dot(normal, p) = offset + k * pitch, k = 0 .. layers - 1 (the normal as given, never
+        normalised), as directed segments: the solid lies on the left of a -> b seen from the tip of the normal.  Returns
+        (segments, layer_starts, SliceStats), or without the statistics with want_stats=False: `segments` a structured array
+        {a: 3f4, layer: u4, b: 3f4, node: u4} stably sorted by layer (node-major within a layer), `layer_starts` the layers + 1
+        offsets of the layers in it.  level: as Mesh.  slices.slice_loops chains a layer into closed polylines."""
+        from .slices import SEGMENT
+        opt = _lib.SliceOptions(normal, offset, pitch, layers, level)
+        raw = _lib.CSlice()
+        st = _lib.SliceStats()
+        check(lib.sdfhip_scene_slice(self._h, ctypes.byref(opt), ctypes.byref(raw), ctypes.byref(st) if want_stats else None))
+        try:
+            n = raw.n_segments
+            segs = np.ctypeslib.as_array(ctypes.cast(raw.segments, ctypes.POINTER(ctypes.c_uint32)), shape=(n, 8)).copy().view(SEGMENT).reshape(n) \
+                if n else np.zeros(0, SEGMENT)
+            counts = np.ctypeslib.as_array(raw.layer_counts, shape=(raw.layers,)).copy()
+        finally:
+            lib.sdfhip_slice_free(ctypes.byref(raw))
+        starts = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        segs = segs[np.argsort(segs["layer"], kind="stable")]
+        return (segs, starts, st) if want_stats else (segs, starts)
+
+    def SliceDevice(self, out_ptr=None, capacity=0, counts_ptr=None, normal=(0.0, 0.0, 1.0), offset=0.5, pitch=0.0, layers=1, level=-1, stream=None):
+        """The record count of Slice -- always -- and, if it fits `capacity` records, the 32-byte records into device memory at
+        `out_ptr`, asynchronously on `stream` (a raw hipStream_t value or None), as MeshDevice; in node-major order, NOT sorted by
+        layer.  counts_ptr: `layers` words of device memory for the records per layer, written whether or not the records fit."""
+        opt = _lib.SliceOptions(normal, offset, pitch, layers, level)
+        n = ctypes.c_uint32()
+        check(lib.sdfhip_scene_slice_device(self._h, ctypes.byref(opt), ctypes.c_void_p(int(out_ptr)) if out_ptr else None, int(capacity),
+                                            ctypes.c_void_p(int(counts_ptr)) if counts_ptr else None, ctypes.byref(n),
+                                            ctypes.c_void_p(int(stream)) if stream else None))
+        return n.value
+
     def close(self):
         if self._h:
             lib.sdfhip_scene_free(self._h)
