@@ -1,7 +1,7 @@
 """What surface extraction costs (sdfhip_scene_mesh_device), on cfg-2's 28 M-node scene (dragon_standin(9))
 and on the depth-10 knot scene (OctData.SdfGen(knot_point_cloud(), 10)), at level -1 (the leaves) and level 6:
 
-  count        the count pass alone (k_mesh_count + k_mesh_scan and the 16-byte copy of the total): MeshDevice() with no buffer
+  count        the count pass alone (k_mesh_count + the chunk scan and the 16-byte copy of the total): MeshDevice() with no buffer
   count_emit   count, the host's wait for the total, and k_mesh_emit into a device buffer that fits: MeshDevice(buffer, capacity)
   per second   triangles per second of count_emit; output bytes (72 per triangle)
   against      the time sdfhip_device_bandwidth's read_gbs gives for ONE read of the scene's records (16 bytes per node); the pass reads

@@ -2,7 +2,7 @@
 (dragon_standin(9)) at level -1: one plane, 100 layers and 1000 layers through the whole cube, along z and along the oblique unit
 normal (0.6, 0, 0.8), beside the route it replaces, Scene.Mesh's count + emit of the same scene and level.
 
-  count        the count pass alone (k_slice_count + k_slice_scan and the copy of the total): SliceDevice() with no buffer
+  count        the count pass alone (k_slice_count + the chunk scan and the copy of the total): SliceDevice() with no buffer
   count_emit   count, the host's wait for the total, and k_slice_emit into a device buffer that fits: SliceDevice(buffer, capacity, counts)
   host form    Scene.Slice once: its statistics (kernel_ms; total_ms, the whole C call with the copy to the host -- the binding's sort
                by layer is not in it; cells_cut, cells_crossed, the fullest layer)

@@ -1,8 +1,8 @@
 // The cells of a resident scene and their Kuhn tetrahedra (gfx950): what surface extraction (mesh_kernels.h), the measure
-// (measure_kernels.h) and the nearest-surface search (distance_kernels.h) share, so that the contracts read one definition -- which
-// nodes are cells of a level, which corners are inside, the six tetrahedra and their triangles, where a cut edge's vertex sits, the
-// climb for a node's depth.  Non-template device helpers and one constant table;
-// no kernel.  The rule is N7's (include/sdfhip.h, sdfhip_scene_mesh).
+// (measure_kernels.h), the cross-sections (slice_kernels.h) and the nearest-surface search (distance_kernels.h, so blend.hip too)
+// share, so that the contracts read one definition -- which nodes are cells of a level and which of those are cut, which corners
+// are inside, the six tetrahedra and their triangles, where a cut edge's vertex sits, the climb for a node's depth and coordinates,
+// the record a pass streams.  Non-template device helpers and one constant table; no kernel.  The rule is N7's (include/sdfhip.h, sdfhip_scene_mesh).
 #pragma once
 #include "raymarch_device.h"
 
@@ -90,11 +90,47 @@ __device__ __forceinline__ int node_depth(const NodeRec *__restrict__ nodes, uin
     return d;
 }
 
+// ... and, for the passes that place the cell, its integer coordinates of that depth too: the octant within the parent is index -
+// parent.children, three bits per level.  The same bound and the same links as node_depth, so the two agree on every tree.
+__device__ __forceinline__ int cell_climb(const NodeRec *__restrict__ nodes, uint32_t n, uint32_t i, int32_t parent, uint32_t &cx, uint32_t &cy, uint32_t &cz)
+{
+    int depth = 0;
+    cx = 0; cy = 0; cz = 0;
+    while (parent >= 0 && (uint32_t)parent < n && depth <= MESH_MAX_DEPTH) {
+        const uint2 p = *reinterpret_cast<const uint2 *>(nodes + parent);        // {its parent, its children}
+        const uint32_t oct = i - p.y;
+        cx |= (oct & 1u) << depth; cy |= ((oct >> 1) & 1u) << depth; cz |= ((oct >> 2) & 1u) << depth;
+        i = (uint32_t)parent;
+        parent = (int32_t)p.x;
+        depth++;
+    }
+    return depth;
+}
+
+// Record i as a cell pass streams it.  Past the end: an internal node with no parent and bytes 0.  Every user also tests i < n
+// before it counts or emits anything, so what stands past the end decides nothing: bytes of 0xFF (no inside corner) would do as well.
+__device__ __forceinline__ NodeRec cell_record(const NodeRec *__restrict__ nodes, uint32_t n, uint32_t i)
+{
+    return i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+}
+
 // is node (children, depth) a cell of `level`: -1 = the leaves; L = the leaves of depth <= L and the internal nodes of depth L
 __device__ __forceinline__ bool is_cell(int32_t children, int level, int depth)
 {
     const bool leaf = children < 0;
     return level < 0 ? leaf : (leaf ? depth <= level : depth == level);
+}
+// ... for a pass that has not climbed: the links are walked only where the level needs the depth
+__device__ __forceinline__ bool is_cell(const NodeRec *__restrict__ nodes, uint32_t n, const NodeRec &r, int level)
+{
+    return level < 0 ? (int32_t)r.y < 0 : is_cell((int32_t)r.y, level, node_depth(nodes, n, (int32_t)r.x));
+}
+// are the bytes mixed (some corner inside, some outside): a cell is cut when they are.  is_cut_cell tests the bytes first, so
+// that only mixed nodes walk
+__device__ __forceinline__ bool is_mixed(uint32_t in8) { return in8 != 0u && in8 != 0xFFu; }
+__device__ __forceinline__ bool is_cut_cell(const NodeRec *__restrict__ nodes, uint32_t n, const NodeRec &r, int level, uint32_t in8)
+{
+    return is_mixed(in8) && is_cell(nodes, n, r, level);
 }
 
 }  // namespace sdfhip

@@ -8,8 +8,6 @@
 namespace sdfhip {
 namespace levels {
 
-constexpr int MAX_DEVICES = 64;
-
 // sdfhip_scene_mesh's refusal: the surface is its triangles
 inline int check_source(const char *what, const Source &src)
 {
@@ -17,11 +15,6 @@ inline int check_source(const char *what, const Source &src)
         return fail(SDFHIP_ERR_BAD_TREE, "%s: the tree is not consistent (or deeper than %d levels): it has no mesh, so no surface to measure from", what,
                     MESH_MAX_DEPTH);
     if (src.device < 0 || src.device >= MAX_DEVICES) return fail(SDFHIP_ERR_ARG, "%s: device %d", what, src.device);
-    return SDFHIP_OK;
-}
-inline int check_level(const char *what, int32_t level)
-{
-    if (level < -1 || level > MESH_MAX_DEPTH) return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, level, MESH_MAX_DEPTH);
     return SDFHIP_OK;
 }
 

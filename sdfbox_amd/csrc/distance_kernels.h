@@ -52,8 +52,7 @@ static __global__ __launch_bounds__(DIST_THREADS) void k_dist_mark(const NodeRec
         const NodeRec r = nodes[j];
         // the mesh's own test (k_mesh_emit): mixed bytes, and a cell of the level
         const uint32_t in8 = inside_bits(r.z, r.w);
-        if (in8 == 0u || in8 == 0xFFu) continue;
-        if (!(level < 0 ? (int32_t)r.y < 0 : is_cell((int32_t)r.y, level, node_depth(nodes, n, (int32_t)r.x)))) continue;
+        if (!is_cut_cell(nodes, n, r, level, in8)) continue;
         uint32_t cur = (uint32_t)j;
         int32_t parent = (int32_t)r.x;
         for (int d = 0; d <= MESH_MAX_DEPTH; d++) {

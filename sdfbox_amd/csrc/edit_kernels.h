@@ -7,7 +7,7 @@
 #include "raymarch_device.h"
 #include "sdf_bytes.h"
 #include "sdf_interp.h"      // edit_lerp, trilerp
-#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap
+#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap, lane_rank
 
 namespace sdfhip {
 
@@ -59,12 +59,7 @@ __device__ __forceinline__ bool edit_splits(const EditBrush &B, const float pre[
     return B.carve ? -sc > vc : sc < vc;
 }
 
-__device__ __forceinline__ uint32_t lane_rank(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// One wave's splits to the level's list: slots by ballot + mbcnt and one atomic; the split's bit in the index bitmap (its block's
+// One wave's splits to the level's list: slots by ballot + lane_rank (scan_device.h) and one atomic; the split's bit in the index bitmap (its block's
 // rank among the level's splits is the bitmap's prefix count, edit.hip); the level's lowest and highest split index
 __device__ __forceinline__ void push_split(bool split, const EditSplit &e, EditSplit *__restrict__ list, uint32_t *__restrict__ bitmap,
                                            EditCounters *__restrict__ cnt)

@@ -272,4 +272,96 @@ template <int N> struct CallFrame {
     float total_ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+// ---- the passes over a scene's cells that return no tree: mesh.hip, slice.hip, measure.hip ("The cell pass") ----
+
+// (the texts below print TREE_MAX_DEPTH where the cell passes' own checks printed cell_tets.h's MESH_MAX_DEPTH: both are LM)
+static_assert(TREE_MAX_DEPTH == LM, "one depth limit: cell_tets.h's MESH_MAX_DEPTH is LM too");
+constexpr int MAX_DEVICES = 64;                     // (query.hip keeps a constant of this name and value for its staging buffers)
+constexpr size_t HEAD_BYTES = 256;                  // a pass's header (its totals and counts), in front of what it keeps per chunk
+constexpr size_t KEEP_BYTES = (size_t)16 << 20;     // a block up to this size stays allocated between calls
+
+// what every call on the surface's cells refuses of a level and of a handle; none: "no mesh", "no slice", "no measure"
+inline int check_level(const char *what, int32_t level)
+{
+    if (level < -1 || level > TREE_MAX_DEPTH) return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, level, TREE_MAX_DEPTH);
+    return SDFHIP_OK;
+}
+inline int check_cell_scene(const char *what, const sdfhip_scene *s, const char *none)
+{
+    if (!s->stack_ok || s->depth > (uint32_t)TREE_MAX_DEPTH)
+        return fail(SDFHIP_ERR_BAD_TREE, "%s: the tree is not consistent (or deeper than %d levels): %s", what, TREE_MAX_DEPTH, none);
+    if (s->device < 0 || s->device >= MAX_DEVICES) return fail(SDFHIP_ERR_ARG, "%s: device %d", what, s->device);
+    return SDFHIP_OK;
+}
+
+// A feature's temporaries on one device: a header of HEAD_BYTES and the per-chunk array behind it.  They cannot live in the scene
+// handle (scene.h belongs to the renderer's measured sources), so each feature keeps an array of these, one per device, and a call
+// holds `lock` (before the handle's) from its first use to release().  An emit may be left in flight on the caller's stream: the
+// next call waits for it through `busy`, the library's own event, never through that stream, before it writes the block again.
+// (A synchronous user such as the measure never emits: begin() creates its `busy` too, and it stays unused.)
+struct DeviceScratch {
+    std::mutex lock;
+    char *buf = nullptr;
+    size_t cap = 0;
+    hipEvent_t busy = nullptr, ev0 = nullptr, ev1 = nullptr;
+    bool pending = false;                           // an emit that reads buf may be in flight: `busy` is behind it
+
+    template <class H> H *head() { return reinterpret_cast<H *>(buf); }
+    template <class T> T *behind_head() { return reinterpret_cast<T *>(buf + HEAD_BYTES); }
+
+    // The block idle, `need` bytes large and its header zeroed on `st`.  of: what the out-of-memory refusal says the bytes are for.
+    int begin(const char *what, AllocFault &fault, size_t need, const char *of, hipStream_t st)
+    {
+        if (!busy) HIP_TRY(hipEventCreateWithFlags(&busy, hipEventDisableTiming));       // each on its own: one may fail and the next call tries again
+        if (!ev0) HIP_TRY(hipEventCreate(&ev0));
+        if (!ev1) HIP_TRY(hipEventCreate(&ev1));
+        if (pending) { HIP_TRY(hipEventSynchronize(busy)); pending = false; }
+        if (fault.next() || grow_buffer(buf, cap, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %zu bytes of %s", what, need, of);
+        }
+        HIP_TRY(hipMemsetAsync(buf, 0, HEAD_BYTES, st));
+        return SDFHIP_OK;
+    }
+    // launch(): the kernels that fill the header, on `st`.  When this returns they have run and *h is the header; *ms (when given)
+    // is their time.
+    template <class H, class Launch> int count(hipStream_t st, Launch launch, H *h, float *ms)
+    {
+        static_assert(sizeof(H) <= HEAD_BYTES, "the header's room in front of the per-chunk array");
+        if (ms) HIP_TRY(hipEventRecord(ev0, st));
+        launch();
+        HIP_TRY(hipGetLastError());
+        if (ms) HIP_TRY(hipEventRecord(ev1, st));
+        HIP_TRY(hipMemcpyAsync(h, buf, sizeof(H), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (ms) HIP_TRY(hipEventElapsedTime(ms, ev0, ev1));
+        return SDFHIP_OK;
+    }
+    // launch(): the kernel that reads the block and writes the output, left in flight on `st`; the block stays busy until it has run
+    template <class Launch> int emit(hipStream_t st, Launch launch)
+    {
+        launch();
+        pending = true;                             // (whatever the launch said: the wait is harmless)
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(busy, st));
+        return SDFHIP_OK;
+    }
+    // ... the same, then copy_out() -- the copies to the host, on `st` -- and the wait: nothing is in flight; *ms: the emit's time
+    template <class Launch, class Copy> int emit_to_host(hipStream_t st, Launch launch, Copy copy_out, float *ms)
+    {
+        HIP_TRY(hipEventRecord(ev0, st));
+        if (const int rc = emit(st, launch)) return rc;
+        HIP_TRY(hipEventRecord(ev1, st));
+        if (const int rc = copy_out()) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        pending = false;
+        HIP_TRY(hipEventElapsedTime(ms, ev0, ev1));
+        return SDFHIP_OK;
+    }
+    // A call that frees buffers of its own (the host forms) settles first: nothing of it is in flight on `st` when they go, however
+    // it ended.  Every call ends with release(): the block goes when it is idle and above KEEP_BYTES.
+    void settle(hipStream_t st) { if (pending) { (void)hipStreamSynchronize(st); pending = false; } }
+    void release() { if (!pending) release_buffer(buf, cap, KEEP_BYTES); }
+};
+
 }  // namespace sdfhip

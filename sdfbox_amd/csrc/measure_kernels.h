@@ -224,33 +224,22 @@ __global__ __launch_bounds__(MEASURE_THREADS) void k_measure_cells(const NodeRec
     const uint32_t base = blockIdx.x * MEASURE_CHUNK + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (threadIdx.x < 16u) hist[threadIdx.x] = 0u;
-    // past the end: internal, no cell of any level.  The next row's record is in flight while this row's cell is measured.
-    const auto record = [&](uint32_t i) { return i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu); };
-    NodeRec ahead = record(base);
+    // the next row's record is in flight while this row's cell is measured
+    NodeRec ahead = cell_record(nodes, n, base);
     __syncthreads();
     // (one copy of the cell arithmetic, not one per row)
 #pragma unroll 1
     for (int k = 0; k < MEASURE_ROWS; k++) {
         const uint32_t i = base + (uint32_t)k * MEASURE_THREADS;
         const NodeRec rec = ahead;
-        if (k + 1 < MEASURE_ROWS) ahead = record(i + MEASURE_THREADS);
+        if (k + 1 < MEASURE_ROWS) ahead = cell_record(nodes, n, i + MEASURE_THREADS);
         const bool leaf = (int32_t)rec.y < 0;
-        // the climb: depth and the coordinates of that depth, from the links (the octant within the parent is index - parent.children)
         MeasureCell c;
         c.cx = 0; c.cy = 0; c.cz = 0;
         int depth = 0;
         bool cell = false;
         if (i < n && (level >= 0 || leaf)) {
-            uint32_t cur = i;
-            int32_t parent = (int32_t)rec.x;
-            while (parent >= 0 && (uint32_t)parent < n && depth <= MESH_MAX_DEPTH) {
-                const uint2 p = *reinterpret_cast<const uint2 *>(nodes + parent);        // {its parent, its children}
-                const uint32_t oct = cur - p.y;
-                c.cx |= (oct & 1u) << depth; c.cy |= ((oct >> 1) & 1u) << depth; c.cz |= ((oct >> 2) & 1u) << depth;
-                cur = (uint32_t)parent;
-                parent = (int32_t)p.x;
-                depth++;
-            }
+            depth = cell_climb(nodes, n, i, (int32_t)rec.x, c.cx, c.cy, c.cz);
             cell = is_cell((int32_t)rec.y, level, depth);
         }
         const uint32_t in8 = inside_bits(rec.z, rec.w);

@@ -4,12 +4,10 @@
 // Replaces: nothing in the reference's code.  Its tree only ever becomes pixels; a scene built, carved and picked here had no way
 // out as geometry.
 //
-// Per call: k_mesh_count and k_mesh_scan on the call's stream, one host synchronisation for the triangle total (it sizes the output
+// Per call: k_mesh_count and the chunk scan on the call's stream, one host synchronisation for the triangle total (it sizes the output
 // and is what the _device form always returns), then k_mesh_emit.  The _device form leaves the emit in flight on the caller's stream;
 // the host form runs on the scene's own stream, copies the vertices out and waits.  The temporaries (four bytes per 1024 nodes and a
-// 16-byte header) cannot live in the scene handle (scene.h belongs to the renderer's measured sources): one block per device is kept
-// here, and a call waits for the emit that last read it -- through the library's own event, never the caller's stream -- before it
-// writes it again.
+// 16-byte header) are one DeviceScratch per device; the steps round the launches are its (host_support.h).
 #include "mesh_kernels.h"
 #include "host_support.h"
 #include "abi_guard.h"
@@ -25,19 +23,9 @@ static_assert(sizeof(sdfhip_mesh_options) == 8 && sizeof(sdfhip_mesh_stats) == 2
 
 namespace {
 
-constexpr int MAX_DEVICES = 64;
-constexpr size_t HEAD_BYTES = 256;                  // the header's own lines, in front of the chunk totals
-constexpr size_t KEEP_BYTES = (size_t)16 << 20;     // a block up to this size stays allocated between calls
 constexpr unsigned long long MAX_TRIANGLES = 0x7FFFFFFFull;
 
-struct Temp {
-    std::mutex lock;
-    char *buf = nullptr;
-    size_t cap = 0;
-    hipEvent_t busy = nullptr, ev0 = nullptr, ev1 = nullptr;
-    bool pending = false;                           // an emit that reads buf may be in flight: `busy` is behind it
-};
-Temp g_temp[MAX_DEVICES];
+DeviceScratch g_temp[MAX_DEVICES];
 
 // The vertices are stored with plain 16-byte stores: 2.15 against 2.92 ms with non-temporal ones for the 27.5 M triangles of the 28 M-node
 // scene, 4.59 ms with 8-byte stores (count + emit; profiles/mesh_bench.json) -- unlike the query records, a lane's triangles are neighbours of the next
@@ -59,64 +47,39 @@ int check_options(const char *what, const sdfhip_mesh_options *opt, int32_t *lev
     *level = -1;
     if (!opt) return SDFHIP_OK;
     if (const int rc = check_options_size(what, opt, sizeof(sdfhip_mesh_options), "sdfhip_mesh_options_default sets the size")) return rc;
-    if (opt->level < -1 || opt->level > MESH_MAX_DEPTH)
-        return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, opt->level, MESH_MAX_DEPTH);
+    if (const int rc = check_level(what, opt->level)) return rc;
     *level = opt->level;
     return SDFHIP_OK;
 }
 
-int check_scene(const char *what, const sdfhip_scene *s)
-{
-    if (!s->stack_ok || s->depth > (uint32_t)MESH_MAX_DEPTH)
-        return fail(SDFHIP_ERR_BAD_TREE, "%s: the tree is not consistent (or deeper than %d levels): no mesh", what, MESH_MAX_DEPTH);
-    if (s->device < 0 || s->device >= MAX_DEVICES) return fail(SDFHIP_ERR_ARG, "%s: device %d", what, s->device);
-    return SDFHIP_OK;
-}
-
 uint32_t chunks_of(uint32_t n) { return (uint32_t)(((uint64_t)n + MESH_CHUNK - 1) / MESH_CHUNK); }
-uint32_t *chunk_array(Temp &t) { return reinterpret_cast<uint32_t *>(t.buf + HEAD_BYTES); }
-MeshHeader *header(Temp &t) { return reinterpret_cast<MeshHeader *>(t.buf); }
+uint32_t *chunk_array(DeviceScratch &t) { return t.behind_head<uint32_t>(); }
+MeshHeader *header(DeviceScratch &t) { return t.head<MeshHeader>(); }
 
-// Under the device's Temp lock and the handle's lock, on its device: count and scan on `st`, the header on the host when this returns.
-int count_pass(sdfhip_scene *s, const char *what, Temp &t, Knobs &knobs, int32_t level, bool want_stats, hipStream_t st, MeshHeader *h, float *ms)
+// Under the DeviceScratch's lock and the handle's lock, on its device: count and scan on `st`, the header on the host when this returns.
+int count_pass(sdfhip_scene *s, const char *what, DeviceScratch &t, Knobs &knobs, int32_t level, bool want_stats, hipStream_t st, MeshHeader *h, float *ms)
 {
-    if (!t.busy) HIP_TRY(hipEventCreateWithFlags(&t.busy, hipEventDisableTiming));       // each on its own: one may fail and the next call tries again
-    if (!t.ev0) HIP_TRY(hipEventCreate(&t.ev0));
-    if (!t.ev1) HIP_TRY(hipEventCreate(&t.ev1));
-    if (t.pending) { HIP_TRY(hipEventSynchronize(t.busy)); t.pending = false; }
     const uint32_t nchunk = chunks_of(s->n);
-    const size_t need = HEAD_BYTES + (size_t)nchunk * sizeof(uint32_t);
-    if (knobs.alloc.next() || grow_buffer(t.buf, t.cap, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %zu bytes of chunk totals", what, need);
-    }
-    HIP_TRY(hipMemsetAsync(t.buf, 0, HEAD_BYTES, st));
-    if (ms) HIP_TRY(hipEventRecord(t.ev0, st));
-    if (want_stats) hipLaunchKernelGGL(k_mesh_count<true>, dim3(nchunk), dim3(MESH_THREADS), 0, st, s->nodes, s->n, level, chunk_array(t), header(t));
-    else hipLaunchKernelGGL(k_mesh_count<false>, dim3(nchunk), dim3(MESH_THREADS), 0, st, s->nodes, s->n, level, chunk_array(t), header(t));
-    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, st, chunk_array(t), nchunk, header(t));
-    HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(hipEventRecord(t.ev1, st));
-    HIP_TRY(hipMemcpyAsync(h, t.buf, sizeof(MeshHeader), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, t.ev0, t.ev1));
+    if (const int rc = t.begin(what, knobs.alloc, HEAD_BYTES + (size_t)nchunk * sizeof(uint32_t), "chunk totals", st)) return rc;
+    const auto launch = [&] {
+        if (want_stats) hipLaunchKernelGGL(k_mesh_count<true>, dim3(nchunk), dim3(MESH_THREADS), 0, st, s->nodes, s->n, level, chunk_array(t), header(t));
+        else hipLaunchKernelGGL(k_mesh_count<false>, dim3(nchunk), dim3(MESH_THREADS), 0, st, s->nodes, s->n, level, chunk_array(t), header(t));
+        hipLaunchKernelGGL(k_scan_chunk_totals<unsigned long long>, dim3(1), dim3(1024), 0, st, chunk_array(t), nchunk, &header(t)->n_triangles);
+    };
+    if (const int rc = t.count(st, launch, h, ms)) return rc;
     if (h->n_triangles > MAX_TRIANGLES)
         return fail(SDFHIP_ERR_ARG, "%s: the mesh would have %llu triangles, more than 2^31 - 1", what, h->n_triangles);
     return SDFHIP_OK;
 }
 
-// ... the emit behind it on `st`; the block stays busy until it has run
-int emit_pass(sdfhip_scene *s, Temp &t, const Knobs &knobs, int32_t level, float *d_verts6, hipStream_t st)
+// ... the emit's launch behind it on `st`
+void launch_emit(sdfhip_scene *s, DeviceScratch &t, const Knobs &knobs, int32_t level, float *d_verts6, hipStream_t st)
 {
     const dim3 grid(chunks_of(s->n)), block(MESH_THREADS);
     if (knobs.nt && knobs.wide) hipLaunchKernelGGL((k_mesh_emit<true, true>), grid, block, 0, st, s->nodes, s->n, level, chunk_array(t), d_verts6);
     else if (knobs.nt) hipLaunchKernelGGL((k_mesh_emit<true, false>), grid, block, 0, st, s->nodes, s->n, level, chunk_array(t), d_verts6);
     else if (knobs.wide) hipLaunchKernelGGL((k_mesh_emit<false, true>), grid, block, 0, st, s->nodes, s->n, level, chunk_array(t), d_verts6);
     else hipLaunchKernelGGL((k_mesh_emit<false, false>), grid, block, 0, st, s->nodes, s->n, level, chunk_array(t), d_verts6);
-    t.pending = true;                               // (whatever the launch said: the wait is harmless)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t.busy, st));
-    return SDFHIP_OK;
 }
 
 }  // namespace
@@ -138,8 +101,8 @@ try {
     int32_t level;
     if (const int rc = check_options(what, opt, &level)) return rc;
     if (capacity_triangles && !d_verts6) return fail(SDFHIP_ERR_ARG, "%s: a capacity of %u triangles and no buffer", what, capacity_triangles);
-    if (const int rc = check_scene(what, scene)) return rc;
-    Temp &t = g_temp[scene->device];
+    if (const int rc = check_cell_scene(what, scene, "no mesh")) return rc;
+    DeviceScratch &t = g_temp[scene->device];
     Knobs knobs;
     std::lock_guard<std::mutex> hold(t.lock);
     std::lock_guard<std::mutex> lk(scene->lock);
@@ -150,9 +113,9 @@ try {
     int rc = count_pass(scene, what, t, knobs, level, false, st, &h, nullptr);
     if (rc == SDFHIP_OK) {
         *n_triangles = (uint32_t)h.n_triangles;
-        if (h.n_triangles && h.n_triangles <= capacity_triangles) rc = emit_pass(scene, t, knobs, level, d_verts6, st);
+        if (h.n_triangles && h.n_triangles <= capacity_triangles) rc = t.emit(st, [&] { launch_emit(scene, t, knobs, level, d_verts6, st); });
     }
-    if (!t.pending) release_buffer(t.buf, t.cap, KEEP_BYTES);
+    t.release();
     return rc;
 }
 SDFHIP_ABI_CATCH(sdfhip_scene_mesh_device)
@@ -165,8 +128,8 @@ try {
     out->n_triangles = 0; out->verts6 = nullptr;
     int32_t level;
     if (const int rc = check_options(what, opt, &level)) return rc;
-    if (const int rc = check_scene(what, scene)) return rc;
-    Temp &t = g_temp[scene->device];
+    if (const int rc = check_cell_scene(what, scene, "no mesh")) return rc;
+    DeviceScratch &t = g_temp[scene->device];
     Knobs knobs;
     std::lock_guard<std::mutex> hold(t.lock);
     DeviceGuard g(scene->device);
@@ -187,18 +150,12 @@ try {
         }
         verts = knobs.alloc.next() ? nullptr : static_cast<float *>(malloc(bytes));
         if (!verts) return fail(SDFHIP_ERR_NOMEM, "%s: out of host memory for %llu triangles (%zu bytes)", what, h.n_triangles, bytes);
-        HIP_TRY(hipEventRecord(t.ev0, st));
-        if (const int r = emit_pass(scene, t, knobs, level, d_verts, st)) return r;
-        HIP_TRY(hipEventRecord(t.ev1, st));
-        HIP_TRY(hipMemcpyAsync(verts, d_verts, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        t.pending = false;
-        HIP_TRY(hipEventElapsedTime(&emit_ms, t.ev0, t.ev1));
-        return SDFHIP_OK;
+        const auto copy_out = [&]() -> int { HIP_TRY(hipMemcpyAsync(verts, d_verts, bytes, hipMemcpyDeviceToHost, st)); return SDFHIP_OK; };
+        return t.emit_to_host(st, [&] { launch_emit(scene, t, knobs, level, d_verts, st); }, copy_out, &emit_ms);
     }();
-    if (rc != SDFHIP_OK && t.pending) { (void)hipStreamSynchronize(scene->stream); t.pending = false; }   // nothing of this call is in flight when its buffers go
+    t.settle(scene->stream);
     release_buffer(d_verts, d_cap);
-    release_buffer(t.buf, t.cap, KEEP_BYTES);
+    t.release();
     if (rc != SDFHIP_OK) { free(verts); return rc; }
     out->n_triangles = (uint32_t)h.n_triangles;
     out->verts6 = verts;

@@ -12,15 +12,15 @@
 // count -> scan -> emit, and both ends stream the records:
 //   k_mesh_count   one lane per node, MESH_CHUNK nodes per workgroup: one 16-byte load gives links and bytes; the chunk's triangle
 //                  total goes to chunk[]; cells and cut cells are counted beside it
-//   k_mesh_scan    the chunks' totals -> exclusive prefix (one workgroup), and the grand total as 64 bits
+//   the scan       scan_device.h's k_scan_chunk_totals: the chunks' totals -> exclusive prefix (one workgroup), the grand total as 64 bits
 //   k_mesh_emit    the same lanes read the same records again, recount, take their offset from the chunk's prefix and a scan inside
 //                  the workgroup (shuffles within a wave, LDS across the four), and the lanes whose cell is cut walk up the parent
 //                  links for their coordinates (at most 12 dependent 8-byte loads) and write their triangles
 // Reading the records twice (2 x 16 bytes per node) is cheaper than a per-node count array written, scanned and read back, and
 // keeps the temporary memory at four bytes per 1024 nodes.
 #pragma once
-#include "cell_tets.h"      // the cells, their tetrahedra and triangles (shared with measure_kernels.h)
-#include "scan_device.h"     // block_exclusive_scan
+#include "cell_tets.h"      // the cells, their tetrahedra and triangles, the climb, the streamed record
+#include "scan_device.h"     // k_scan_chunk_totals, wave_sum, wave_scan, ordered_first
 
 namespace sdfhip {
 
@@ -28,37 +28,18 @@ constexpr int MESH_THREADS = 256;
 constexpr int MESH_ROWS = 4;                                  // rows of MESH_THREADS consecutive nodes per workgroup
 constexpr uint32_t MESH_CHUNK = MESH_THREADS * MESH_ROWS;
 
-// what the passes count beside the triangles: 64-bit triangle total (k_mesh_scan), cells of the level, cells whose bytes are mixed
+// what the passes count beside the triangles: 64-bit triangle total (the scan's), cells of the level, cells whose bytes are mixed
 struct MeshHeader { unsigned long long n_triangles; uint32_t cells, cells_cut; };
-
+static_assert(offsetof(MeshHeader, n_triangles) == 0, "the scan writes the total to the header's first eight bytes");
 
 // A node's triangle count, and whether it is a cell and a cut one (for the statistics)
 __device__ __forceinline__ uint32_t node_triangles(const NodeRec *__restrict__ nodes, uint32_t n, const NodeRec &r, int level, bool &cell, bool &cut)
 {
     const uint32_t in8 = inside_bits(r.z, r.w);
-    const bool mixed = in8 != 0u && in8 != 0xFFu;
     // (the statistics count the level's cells, so for a level >= 0 the flat nodes walk for their depth too)
-    cell = level < 0 ? (int32_t)r.y < 0 : is_cell((int32_t)r.y, level, node_depth(nodes, n, (int32_t)r.x));
-    cut = cell && mixed;
+    cell = is_cell(nodes, n, r, level);
+    cut = cell && is_mixed(in8);
     return cut ? cell_triangles(in8) : 0u;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
-        if (lane >= (uint32_t)o) v += u;
-    }
-    return v;
 }
 
 // STATS: also count the level's cells and cut cells into the header (the flat nodes of a level >= 0 then walk for their depth too)
@@ -72,7 +53,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_count(const NodeRec *__re
 #pragma unroll
     for (int k = 0; k < MESH_ROWS; k++) {
         const uint32_t i = base + (uint32_t)k * MESH_THREADS;
-        r[k] = i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);          // past the end: internal, flat, no cell of any level
+        r[k] = cell_record(nodes, n, i);
     }
     uint32_t tris = 0, cells = 0, cuts = 0;
 #pragma unroll
@@ -84,7 +65,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_count(const NodeRec *__re
             tris += node_triangles(nodes, n, r[k], level, cell, cut);
         } else {
             const uint32_t in8 = inside_bits(r[k].z, r[k].w);
-            if (in8 != 0u && in8 != 0xFFu && is_cell((int32_t)r[k].y, level, node_depth(nodes, n, (int32_t)r[k].x))) tris += cell_triangles(in8);
+            if (is_cut_cell(nodes, n, r[k], level, in8)) tris += cell_triangles(in8);
         }
         cells += cell ? 1u : 0u; cuts += cut ? 1u : 0u;
     }
@@ -101,20 +82,6 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_count(const NodeRec *__re
             if (u) atomicAdd(&head->cells_cut, u);
         }
     }
-}
-
-// the chunks' totals -> exclusive prefix in place, in one workgroup (at most 2^21 chunks: 2^31 nodes); sums in 64 bits -- the low
-// words are the offsets the emit uses, which the host side only launches when the total fits 31 bits
-__global__ __launch_bounds__(1024) void k_mesh_scan(uint32_t *__restrict__ chunk, uint32_t nchunk, MeshHeader *__restrict__ head)
-{
-    __shared__ unsigned long long part[1024];
-    const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
-    unsigned long long sum = 0;
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
-    unsigned long long total;
-    unsigned long long run = block_exclusive_scan<unsigned long long, 1024>(sum, part, total);
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = (uint32_t)run; run += v; }
-    if (t == 1023) head->n_triangles = total;
 }
 
 // A triangle is 72 bytes, so triangle k starts 8 bytes past a 16-byte boundary when k is odd: 16-byte stores with one 8-byte store in
@@ -162,7 +129,7 @@ __device__ __forceinline__ void cut_vertex(const Cell &cell, uint32_t cx, uint32
     o[0] = px; o[1] = py; o[2] = pz; o[3] = gx * rg; o[4] = gy * rg; o[5] = gz * rg;
 }
 
-// chunk[]: the exclusive prefix k_mesh_scan left.  Every lane stays in the kernel through the workgroup's scans; only the vertex work
+// chunk[]: the exclusive prefix the scan left.  Every lane stays in the kernel through the workgroup's scans; only the vertex work
 // is under the lane's own condition.
 template <bool NT, bool WIDE>
 __global__ __launch_bounds__(MESH_THREADS) void k_mesh_emit(const NodeRec *__restrict__ nodes, uint32_t n, int level, const uint32_t *__restrict__ chunk,
@@ -175,7 +142,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_emit(const NodeRec *__res
 #pragma unroll
     for (int k = 0; k < MESH_ROWS; k++) {
         const uint32_t i = base + (uint32_t)k * MESH_THREADS;
-        r[k] = i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+        r[k] = cell_record(nodes, n, i);
     }
     uint32_t cnt[MESH_ROWS], incl[MESH_ROWS];
 #pragma unroll
@@ -183,9 +150,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_emit(const NodeRec *__res
         const uint32_t i = base + (uint32_t)k * MESH_THREADS;
         const uint32_t in8 = inside_bits(r[k].z, r[k].w);
         cnt[k] = 0u;
-        if (i < n && in8 != 0u && in8 != 0xFFu &&
-            (level < 0 ? (int32_t)r[k].y < 0 : is_cell((int32_t)r[k].y, level, node_depth(nodes, n, (int32_t)r[k].x))))
-            cnt[k] = cell_triangles(in8);
+        if (i < n && is_cut_cell(nodes, n, r[k], level, in8)) cnt[k] = cell_triangles(in8);
         incl[k] = wave_scan(cnt[k]);
         if (lane == 63u) part[k][wave] = incl[k];
     }
@@ -193,25 +158,10 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_emit(const NodeRec *__res
     uint32_t run = chunk[blockIdx.x];                     // the first triangle of this row's first wave
 #pragma unroll
     for (int k = 0; k < MESH_ROWS; k++) {
-        uint32_t first = run + incl[k] - cnt[k];
-#pragma unroll
-        for (uint32_t w = 0; w < MESH_THREADS / 64; w++) {
-            if (w < wave) first += part[k][w];
-            run += part[k][w];
-        }
+        uint32_t first = ordered_first(incl[k], cnt[k], part[k], wave, run);
         if (cnt[k] == 0u) continue;
-        // the cell's coordinates of its depth, from the links: the octant within the parent is index - parent.children
-        uint32_t cur = base + (uint32_t)k * MESH_THREADS, cx = 0, cy = 0, cz = 0;
-        int32_t parent = (int32_t)r[k].x;
-        int depth = 0;
-        while (parent >= 0 && (uint32_t)parent < n && depth <= MESH_MAX_DEPTH) {
-            const uint2 p = *reinterpret_cast<const uint2 *>(nodes + parent);        // {its parent, its children}
-            const uint32_t oct = cur - p.y;
-            cx |= (oct & 1u) << depth; cy |= ((oct >> 1) & 1u) << depth; cz |= ((oct >> 2) & 1u) << depth;
-            cur = (uint32_t)parent;
-            parent = (int32_t)p.x;
-            depth++;
-        }
+        uint32_t cx, cy, cz;
+        const int depth = cell_climb(nodes, n, base + (uint32_t)k * MESH_THREADS, (int32_t)r[k].x, cx, cy, cz);
         Cell cell;
         cell.scale = __int_as_float((127 - depth) << 23);                           // 2^-depth
         cell.inv = __int_as_float((127 + depth) << 23);

@@ -9,17 +9,12 @@
 #include "raymarch_device.h"
 #include "sdf_bytes.h"
 #include "sdf_interp.h"
-#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap
+#include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap, lane_rank
 
 namespace sdfhip {
 
 // per level d: the internal nodes of depth d (= the blocks whose parents they are), and how many of those blocks were removed
 struct PruneCounters { uint32_t n_blocks, removed; };
-
-__device__ __forceinline__ uint32_t prune_lane_rank(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 __device__ __forceinline__ bool prune_bit(const uint32_t *bitmap, uint32_t i) { return (bitmap[i >> 5] >> (i & 31u)) & 1u; }
 
@@ -42,7 +37,7 @@ __global__ __launch_bounds__(256) void k_prune_expand(const NodeRec *__restrict_
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(&cnt_next->n_blocks, (uint32_t)__popcll(m));
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            const uint32_t slot = base + prune_lane_rank(m);
+            const uint32_t slot = base + lane_rank(m);
             if (inner && slot < cap) next[slot] = child;
         }
     }

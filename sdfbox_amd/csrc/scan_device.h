@@ -1,4 +1,5 @@
-// The workgroup scan and the bitmap rank that the tree rewriters share (gfx950).  Everything here is a template or
+// The workgroup scan and the bitmap rank that the tree rewriters share, and the chunk scan, the wave sums and the ordered offset of
+// the passes over a scene's cells (mesh, slice; the lane rank is the edit's and the prune's) (gfx950).  Everything here is a template or
 // __device__ __forceinline__, so any .hip may include it -- unlike the kernel headers (edit_kernels.h, prune_kernels.h, ...), whose
 // kernels are not templates and which are therefore included by one translation unit ONLY.  That rule stays: a kernel that is not a
 // template does not belong here.
@@ -64,6 +65,62 @@ template <bool TOTAL> __global__ __launch_bounds__(1024) void k_rank_scan_chunks
     uint32_t run = block_exclusive_scan<uint32_t, 1024>(sum, part, total);
     for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = run; run += v; }
     if (TOTAL && t == 1023) chunk[nchunk] = total;
+}
+
+// ... the same with the sums in 64 bits and the grand total at *total (at most 2^21 chunks of 1024: 2^31 nodes): the scan of the
+// cell passes (count -> scan -> emit: mesh_kernels.h, slice_kernels.h).  The low words are the offsets the emit uses, which the
+// host side only launches when the total fits 31 bits.  A pass's header keeps the total as its first member.
+template <class Total> __global__ __launch_bounds__(1024) void k_scan_chunk_totals(uint32_t *__restrict__ chunk, uint32_t nchunk, Total *__restrict__ total_out)
+{
+    __shared__ Total part[1024];
+    const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
+    Total sum = 0;
+    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
+    Total total;
+    Total run = block_exclusive_scan<Total, 1024>(sum, part, total);
+    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = (uint32_t)run; run += v; }
+    if (t == 1023) *total_out = total;
+}
+
+// ---- within a wave, and from a wave to its workgroup ------------------------------------------------------------------------------
+
+// a lane's rank among the set bits of the ballot m: the set bits below its own
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+// inclusive prefix sum over the wave's lanes
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= (uint32_t)o) v += u;
+    }
+    return v;
+}
+
+// The first output index of a lane that writes cnt records in lane order: incl = wave_scan(cnt); totals[w] = wave w's last incl, stored
+// to LDS before a barrier; run = the first index of the row's first wave on entry, of the next row's on return.  The order is the
+// lanes', whichever wave ran first.
+template <uint32_t WAVES> __device__ __forceinline__ uint32_t ordered_first(uint32_t incl, uint32_t cnt, const uint32_t (&totals)[WAVES], uint32_t wave,
+                                                                            uint32_t &run)
+{
+    uint32_t first = run + incl - cnt;
+#pragma unroll
+    for (uint32_t w = 0; w < WAVES; w++) {
+        if (w < wave) first += totals[w];
+        run += totals[w];
+    }
+    return first;
 }
 
 // The set bits before bit `bit` of the bitmap's word w_rel (counted from the first word that was scanned), whose value is `word`

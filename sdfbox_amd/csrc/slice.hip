@@ -4,11 +4,11 @@
 // Replaces: nothing that runs in the reference.  Its tree only ever becomes pixels; the outline of a solid in a plane, which a
 // printer's slicer, a section view and a fit check start from, had to be picked out of sdfhip_scene_mesh's triangles on the host.
 //
-// Per call, as the mesh (mesh.hip): k_slice_count and k_slice_scan on the call's stream, one host synchronisation for the record total
+// Per call, as the mesh (mesh.hip): k_slice_count and the chunk scan on the call's stream, one host synchronisation for the record total
 // (it sizes the output and is what the _device form always returns), then k_slice_emit.  The _device form leaves the emit in flight on
 // the caller's stream; the host form runs on the scene's own stream, copies the records and the per-layer counts out and waits.  The
-// temporaries (four bytes per 1024 nodes, a header and, for the host form, four bytes per layer) live in one block per device, and a
-// call waits for the emit that last read it -- through the library's own event, never the caller's stream -- before it writes it again.
+// temporaries (four bytes per 1024 nodes, a header and, for the host form, four bytes per layer) are one DeviceScratch per device; the
+// steps round the launches are its (host_support.h).
 #include "slice_kernels.h"
 #include "host_support.h"
 #include "abi_guard.h"
@@ -26,20 +26,10 @@ static_assert(sizeof(sdfhip_slice_options) == 32 && sizeof(sdfhip_segment) == 32
 
 namespace {
 
-constexpr int MAX_DEVICES = 64;
-constexpr size_t HEAD_BYTES = 256;                  // the header's own lines, in front of the chunk totals
-constexpr size_t KEEP_BYTES = (size_t)16 << 20;     // a block up to this size stays allocated between calls
 constexpr unsigned long long MAX_SEGMENTS = 0x7FFFFFFFull;
 constexpr uint32_t MAX_LAYERS = 65536;
 
-struct Temp {
-    std::mutex lock;
-    char *buf = nullptr;
-    size_t cap = 0;
-    hipEvent_t busy = nullptr, ev0 = nullptr, ev1 = nullptr;
-    bool pending = false;                           // an emit that reads buf may be in flight: `busy` is behind it
-};
-Temp g_temp[MAX_DEVICES];
+DeviceScratch g_temp[MAX_DEVICES];
 
 // laboratory library: SDFHIP_SLICE_FAIL_ALLOC=k fails the call's k-th allocation (0 = the first)
 struct Knobs { AllocFault alloc{ "SDFHIP_SLICE_FAIL_ALLOC" }; };
@@ -52,8 +42,7 @@ int check_options(const char *what, const sdfhip_slice_options *opt, Request *rq
     rq->pl = SlicePlanes{ 0.0f, 0.0f, 1.0f, 0.5f, 0.0f, 1u };
     if (!opt) return SDFHIP_OK;
     if (const int rc = check_options_size(what, opt, sizeof(sdfhip_slice_options), "sdfhip_slice_options_default sets the size")) return rc;
-    if (opt->level < -1 || opt->level > MESH_MAX_DEPTH)
-        return fail(SDFHIP_ERR_ARG, "%s: level %d is neither -1 nor 0..%d", what, opt->level, MESH_MAX_DEPTH);
+    if (const int rc = check_level(what, opt->level)) return rc;
     const float *nr = opt->normal;
     if (!std::isfinite(nr[0]) || !std::isfinite(nr[1]) || !std::isfinite(nr[2]) || (nr[0] == 0.0f && nr[1] == 0.0f && nr[2] == 0.0f))
         return fail(SDFHIP_ERR_ARG, "%s: the normal (%g, %g, %g) is not finite or is zero", what, nr[0], nr[1], nr[2]);
@@ -66,60 +55,37 @@ int check_options(const char *what, const sdfhip_slice_options *opt, Request *rq
     return SDFHIP_OK;
 }
 
-int check_scene(const char *what, const sdfhip_scene *s)
-{
-    if (!s->stack_ok || s->depth > (uint32_t)MESH_MAX_DEPTH)
-        return fail(SDFHIP_ERR_BAD_TREE, "%s: the tree is not consistent (or deeper than %d levels): no slice", what, MESH_MAX_DEPTH);
-    if (s->device < 0 || s->device >= MAX_DEVICES) return fail(SDFHIP_ERR_ARG, "%s: device %d", what, s->device);
-    return SDFHIP_OK;
-}
-
 uint32_t chunks_of(uint32_t n) { return (uint32_t)(((uint64_t)n + SLICE_CHUNK - 1) / SLICE_CHUNK); }
-SliceHeader *header(Temp &t) { return reinterpret_cast<SliceHeader *>(t.buf); }
-uint32_t *chunk_array(Temp &t) { return reinterpret_cast<uint32_t *>(t.buf + HEAD_BYTES); }
+SliceHeader *header(DeviceScratch &t) { return t.head<SliceHeader>(); }
+uint32_t *chunk_array(DeviceScratch &t) { return t.behind_head<uint32_t>(); }
 // the host form's per-layer counts, behind the chunk totals
-uint32_t *count_array(Temp &t, uint32_t nchunk) { return chunk_array(t) + nchunk; }
+uint32_t *count_array(DeviceScratch &t, uint32_t nchunk) { return chunk_array(t) + nchunk; }
 
-// Under the device's Temp lock and the handle's lock, on its device: count and scan on `st`, the header on the host when this returns.
+// Under the DeviceScratch's lock and the handle's lock, on its device: count and scan on `st`, the header on the host when this returns.
 // own_counts: the per-layer counts go to the block's own array (the host form); otherwise to d_counts, which may be null.
-int count_pass(sdfhip_scene *s, const char *what, Temp &t, Knobs &knobs, const Request &rq, bool want_stats, bool own_counts, uint32_t *d_counts,
+int count_pass(sdfhip_scene *s, const char *what, DeviceScratch &t, Knobs &knobs, const Request &rq, bool want_stats, bool own_counts, uint32_t *d_counts,
                hipStream_t st, SliceHeader *h, float *ms)
 {
-    if (!t.busy) HIP_TRY(hipEventCreateWithFlags(&t.busy, hipEventDisableTiming));       // each on its own: one may fail and the next call tries again
-    if (!t.ev0) HIP_TRY(hipEventCreate(&t.ev0));
-    if (!t.ev1) HIP_TRY(hipEventCreate(&t.ev1));
-    if (t.pending) { HIP_TRY(hipEventSynchronize(t.busy)); t.pending = false; }
     const uint32_t nchunk = chunks_of(s->n);
     const size_t need = HEAD_BYTES + ((size_t)nchunk + (own_counts ? rq.pl.layers : 0u)) * sizeof(uint32_t);
-    if (knobs.alloc.next() || grow_buffer(t.buf, t.cap, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SDFHIP_ERR_NOMEM, "%s: out of device memory for %zu bytes of chunk totals and layer counts", what, need);
-    }
+    if (const int rc = t.begin(what, knobs.alloc, need, "chunk totals and layer counts", st)) return rc;
     if (own_counts) d_counts = count_array(t, nchunk);
-    HIP_TRY(hipMemsetAsync(t.buf, 0, HEAD_BYTES, st));
     if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)rq.pl.layers * sizeof(uint32_t), st));
-    if (ms) HIP_TRY(hipEventRecord(t.ev0, st));
-    if (want_stats) hipLaunchKernelGGL(k_slice_count<true>, dim3(nchunk), dim3(SLICE_THREADS), 0, st, s->nodes, s->n, rq.level, rq.pl, chunk_array(t), header(t), d_counts);
-    else hipLaunchKernelGGL(k_slice_count<false>, dim3(nchunk), dim3(SLICE_THREADS), 0, st, s->nodes, s->n, rq.level, rq.pl, chunk_array(t), header(t), d_counts);
-    hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, st, chunk_array(t), nchunk, header(t));
-    HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(hipEventRecord(t.ev1, st));
-    HIP_TRY(hipMemcpyAsync(h, t.buf, sizeof(SliceHeader), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, t.ev0, t.ev1));
+    const auto launch = [&] {
+        if (want_stats) hipLaunchKernelGGL(k_slice_count<true>, dim3(nchunk), dim3(SLICE_THREADS), 0, st, s->nodes, s->n, rq.level, rq.pl, chunk_array(t), header(t), d_counts);
+        else hipLaunchKernelGGL(k_slice_count<false>, dim3(nchunk), dim3(SLICE_THREADS), 0, st, s->nodes, s->n, rq.level, rq.pl, chunk_array(t), header(t), d_counts);
+        hipLaunchKernelGGL(k_scan_chunk_totals<unsigned long long>, dim3(1), dim3(1024), 0, st, chunk_array(t), nchunk, &header(t)->n_segments);
+    };
+    if (const int rc = t.count(st, launch, h, ms)) return rc;
     if (h->n_segments > MAX_SEGMENTS)
         return fail(SDFHIP_ERR_ARG, "%s: the slice would have %llu segments, more than 2^31 - 1", what, h->n_segments);
     return SDFHIP_OK;
 }
 
-// ... the emit behind it on `st`; the block stays busy until it has run
-int emit_pass(sdfhip_scene *s, Temp &t, const Request &rq, sdfhip_segment *d_segments, hipStream_t st)
+// ... the emit's launch behind it on `st`
+void launch_emit(sdfhip_scene *s, DeviceScratch &t, const Request &rq, sdfhip_segment *d_segments, hipStream_t st)
 {
     hipLaunchKernelGGL(k_slice_emit, dim3(chunks_of(s->n)), dim3(SLICE_THREADS), 0, st, s->nodes, s->n, rq.level, rq.pl, chunk_array(t), d_segments);
-    t.pending = true;                               // (whatever the launch said: the wait is harmless)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t.busy, st));
-    return SDFHIP_OK;
 }
 
 }  // namespace
@@ -155,8 +121,8 @@ try {
     if (const int rc = check_options(what, opt, &rq)) return rc;
     if (capacity_segments && !d_segments) return fail(SDFHIP_ERR_ARG, "%s: a capacity of %u segments and no buffer", what, capacity_segments);
     if (reinterpret_cast<uintptr_t>(d_segments) & 15u) return fail(SDFHIP_ERR_ARG, "%s: the segment buffer is not 16-byte aligned", what);
-    if (const int rc = check_scene(what, scene)) return rc;
-    Temp &t = g_temp[scene->device];
+    if (const int rc = check_cell_scene(what, scene, "no slice")) return rc;
+    DeviceScratch &t = g_temp[scene->device];
     Knobs knobs;
     std::lock_guard<std::mutex> hold(t.lock);
     std::lock_guard<std::mutex> lk(scene->lock);
@@ -167,9 +133,9 @@ try {
     int rc = count_pass(scene, what, t, knobs, rq, false, false, d_layer_counts, st, &h, nullptr);
     if (rc == SDFHIP_OK) {
         *n_segments = (uint32_t)h.n_segments;
-        if (h.n_segments && h.n_segments <= capacity_segments) rc = emit_pass(scene, t, rq, d_segments, st);
+        if (h.n_segments && h.n_segments <= capacity_segments) rc = t.emit(st, [&] { launch_emit(scene, t, rq, d_segments, st); });
     }
-    if (!t.pending) release_buffer(t.buf, t.cap, KEEP_BYTES);
+    t.release();
     return rc;
 }
 SDFHIP_ABI_CATCH(sdfhip_scene_slice_device)
@@ -182,8 +148,8 @@ try {
     if (!scene || !out) return fail(SDFHIP_ERR_ARG, "%s: null argument", what);
     Request rq;
     if (const int rc = check_options(what, opt, &rq)) return rc;
-    if (const int rc = check_scene(what, scene)) return rc;
-    Temp &t = g_temp[scene->device];
+    if (const int rc = check_cell_scene(what, scene, "no slice")) return rc;
+    DeviceScratch &t = g_temp[scene->device];
     Knobs knobs;
     std::lock_guard<std::mutex> hold(t.lock);
     DeviceGuard g(scene->device);
@@ -213,19 +179,16 @@ try {
         }
         segs = knobs.alloc.next() ? nullptr : static_cast<sdfhip_segment *>(malloc(bytes));
         if (!segs) return fail(SDFHIP_ERR_NOMEM, "%s: out of host memory for %llu segments (%zu bytes)", what, h.n_segments, bytes);
-        HIP_TRY(hipEventRecord(t.ev0, st));
-        if (const int r = emit_pass(scene, t, rq, d_segs, st)) return r;
-        HIP_TRY(hipEventRecord(t.ev1, st));
-        HIP_TRY(hipMemcpyAsync(segs, d_segs, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        t.pending = false;
-        HIP_TRY(hipEventElapsedTime(&emit_ms, t.ev0, t.ev1));
-        return SDFHIP_OK;
+        const auto copy_out = [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(segs, d_segs, bytes, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, st));
+            return SDFHIP_OK;
+        };
+        return t.emit_to_host(st, [&] { launch_emit(scene, t, rq, d_segs, st); }, copy_out, &emit_ms);
     }();
-    if (rc != SDFHIP_OK && t.pending) { (void)hipStreamSynchronize(scene->stream); t.pending = false; }   // nothing of this call is in flight when its buffers go
+    t.settle(scene->stream);
     release_buffer(d_segs, d_cap);
-    release_buffer(t.buf, t.cap, KEEP_BYTES);
+    t.release();
     if (rc != SDFHIP_OK) { free(segs); free(counts); return rc; }
     out->n_segments = (uint32_t)h.n_segments;
     out->segments = segs;

@@ -17,15 +17,15 @@
 //                   records per layer to layer_counts[] (integers: through an LDS histogram up to SLICE_LDS_LAYERS layers, one global
 //                   atomic per layer and workgroup; straight to global memory above), the cells beside them.  Most lanes idle, as in
 //                   the measure: a cut cell is one node in some tens
-//   k_slice_scan    the chunks' totals -> exclusive prefix (one workgroup), and the grand total as 64 bits
+//   the scan        scan_device.h's k_scan_chunk_totals, as the mesh's
 //   k_slice_emit    the same lanes read the same records again, row by row: recount, the offset from the chunk's prefix and a scan
 //                   inside the workgroup (shuffles within a wave, LDS across the four), then the crossings again, each written as two
 //                   16-byte stores
 // One copy of the triangle walk (slice_cell<EMIT>) serves both passes, so that what is counted is what is written.
 #pragma once
 #include "../../include/sdfhip.h"      // sdfhip_segment
-#include "cell_tets.h"      // the cells, their tetrahedra and triangles
-#include "scan_device.h"     // block_exclusive_scan
+#include "cell_tets.h"      // the cells, their tetrahedra and triangles, the climb, the streamed record
+#include "scan_device.h"     // k_scan_chunk_totals, wave_sum, wave_scan, ordered_first
 
 namespace sdfhip {
 
@@ -34,8 +34,9 @@ constexpr int SLICE_ROWS = 4;                                   // rows of SLICE
 constexpr uint32_t SLICE_CHUNK = SLICE_THREADS * SLICE_ROWS;    // 1024 nodes, the mesh's MESH_CHUNK
 constexpr uint32_t SLICE_LDS_LAYERS = 1024;                     // up to this many layers the per-layer counts gather in LDS
 
-// 64-bit record total (k_slice_scan), the level's cells, those with mixed bytes, those that emit at least one record
+// 64-bit record total (the scan's), the level's cells, those with mixed bytes, those that emit at least one record
 struct SliceHeader { unsigned long long n_segments; uint32_t cells, cells_cut, cells_crossed, pad_; };
+static_assert(offsetof(SliceHeader, n_segments) == 0, "the scan writes the total to the header's first eight bytes");
 
 // plane k: dot(normal, p) = offset + (float)k * pitch, the normal as given
 struct SlicePlanes { float nx, ny, nz, offset, pitch; uint32_t layers; };
@@ -172,24 +173,6 @@ __device__ __forceinline__ uint32_t slice_cell(const SlicePlanes &pl, uint32_t v
     return count;
 }
 
-__device__ __forceinline__ uint32_t slice_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ uint32_t slice_wave_scan(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
-        if (lane >= (uint32_t)o) v += u;
-    }
-    return v;
-}
-
 // What a lane knows of its node after the record and, where needed, the climb: is it a cell of the level, is it cut, and for a cut
 // cell the coordinates of its depth.  WALK_ALL: the nodes that are not cut climb for their depth too where the level needs it (the
 // statistics count the level's cells); otherwise only cut candidates climb.
@@ -200,29 +183,15 @@ __device__ __forceinline__ SliceNode slice_node(const NodeRec *__restrict__ node
     SliceNode s;
     s.cell = false; s.cut = false; s.cx = 0; s.cy = 0; s.cz = 0; s.depth = 0;
     if (i >= n) return s;
+    // (is_mixed's test, cell_tets.h, written out: as a call it reaches the compiler's first simplification of the two early returns
+    // below opaque, the kernels' control flow comes out in another order, and k_slice_emit was measurably slower)
     const bool leaf = (int32_t)rec.y < 0, mixed = in8 != 0u && in8 != 0xFFu;
     if (level < 0 && !(leaf && mixed)) { s.cell = leaf; return s; }
     if (!mixed && !WALK_ALL) return s;
-    // the climb: depth and the coordinates of that depth, from the links (the octant within the parent is index - parent.children)
-    uint32_t cur = i;
-    int32_t parent = (int32_t)rec.x;
-    while (parent >= 0 && (uint32_t)parent < n && s.depth <= MESH_MAX_DEPTH) {
-        const uint2 p = *reinterpret_cast<const uint2 *>(nodes + parent);        // {its parent, its children}
-        const uint32_t oct = cur - p.y;
-        s.cx |= (oct & 1u) << s.depth; s.cy |= ((oct >> 1) & 1u) << s.depth; s.cz |= ((oct >> 2) & 1u) << s.depth;
-        cur = (uint32_t)parent;
-        parent = (int32_t)p.x;
-        s.depth++;
-    }
+    s.depth = cell_climb(nodes, n, i, (int32_t)rec.x, s.cx, s.cy, s.cz);
     s.cell = is_cell((int32_t)rec.y, level, s.depth);
     s.cut = s.cell && mixed;
     return s;
-}
-
-// past the end: internal, flat, no cell of any level
-__device__ __forceinline__ NodeRec slice_record(const NodeRec *__restrict__ nodes, uint32_t n, uint32_t i)
-{
-    return i < n ? nodes[i] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
 }
 
 // STATS: also count the level's cells, the cut ones and the crossed ones into the header.  layer_counts: layers words, zeroed by the
@@ -237,7 +206,7 @@ __global__ __launch_bounds__(SLICE_THREADS) void k_slice_count(const NodeRec *__
     const bool in_lds = layer_counts != nullptr && pl.layers <= SLICE_LDS_LAYERS;            // (uniform over the grid)
     if (in_lds) for (uint32_t k = threadIdx.x; k < pl.layers; k += SLICE_THREADS) hist[k] = 0u;
     const uint32_t base = blockIdx.x * SLICE_CHUNK + threadIdx.x;
-    NodeRec ahead = slice_record(nodes, n, base);
+    NodeRec ahead = cell_record(nodes, n, base);
     __syncthreads();
     uint32_t segs = 0, cells = 0, cuts = 0, crossed = 0;
     // (one copy of the cell arithmetic, not one per row; the next row's record is in flight meanwhile)
@@ -245,7 +214,7 @@ __global__ __launch_bounds__(SLICE_THREADS) void k_slice_count(const NodeRec *__
     for (int row = 0; row < SLICE_ROWS; row++) {
         const uint32_t i = base + (uint32_t)row * SLICE_THREADS;
         const NodeRec rec = ahead;
-        if (row + 1 < SLICE_ROWS) ahead = slice_record(nodes, n, i + SLICE_THREADS);
+        if (row + 1 < SLICE_ROWS) ahead = cell_record(nodes, n, i + SLICE_THREADS);
         const uint32_t in8 = inside_bits(rec.z, rec.w);
         const SliceNode s = slice_node<STATS>(nodes, n, i, rec, level, in8);
         cells += s.cell ? 1u : 0u; cuts += s.cut ? 1u : 0u;
@@ -257,8 +226,8 @@ __global__ __launch_bounds__(SLICE_THREADS) void k_slice_count(const NodeRec *__
                                              in_lds ? hist : layer_counts);
         segs += c; crossed += c ? 1u : 0u;
     }
-    segs = slice_wave_sum(segs);
-    if (STATS) { cells = slice_wave_sum(cells); cuts = slice_wave_sum(cuts); crossed = slice_wave_sum(crossed); }
+    segs = wave_sum(segs);
+    if (STATS) { cells = wave_sum(cells); cuts = wave_sum(cuts); crossed = wave_sum(crossed); }
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0u) { part[0][wave] = segs; part[1][wave] = cells; part[2][wave] = cuts; part[3][wave] = crossed; }
     __syncthreads();
@@ -279,21 +248,7 @@ __global__ __launch_bounds__(SLICE_THREADS) void k_slice_count(const NodeRec *__
         }
 }
 
-// the chunks' totals -> exclusive prefix in place, in one workgroup (at most 2^21 chunks: 2^31 nodes); sums in 64 bits -- the low
-// words are the offsets the emit uses, which the host side only launches when the total fits 31 bits
-__global__ __launch_bounds__(1024) void k_slice_scan(uint32_t *__restrict__ chunk, uint32_t nchunk, SliceHeader *__restrict__ head)
-{
-    __shared__ unsigned long long part[1024];
-    const uint32_t t = threadIdx.x, per = (nchunk + 1023u) / 1024u, lo = t * per;
-    unsigned long long sum = 0;
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) sum += chunk[lo + k];
-    unsigned long long total;
-    unsigned long long run = block_exclusive_scan<unsigned long long, 1024>(sum, part, total);
-    for (uint32_t k = 0; k < per; k++) if (lo + k < nchunk) { const uint32_t v = chunk[lo + k]; chunk[lo + k] = (uint32_t)run; run += v; }
-    if (t == 1023) head->n_segments = total;
-}
-
-// chunk[]: the exclusive prefix k_slice_scan left.  Every lane stays in the kernel through the workgroup's scans (one barrier per row);
+// chunk[]: the exclusive prefix the scan left.  Every lane stays in the kernel through the workgroup's scans (one barrier per row);
 // only the cell work is under the lane's own condition.  out holds at least the total's records (the host side checked).
 __global__ __launch_bounds__(SLICE_THREADS) void k_slice_emit(const NodeRec *__restrict__ nodes, uint32_t n, int level, SlicePlanes pl,
                                                               const uint32_t *__restrict__ chunk, sdfhip_segment *__restrict__ out)
@@ -301,28 +256,23 @@ __global__ __launch_bounds__(SLICE_THREADS) void k_slice_emit(const NodeRec *__r
     __shared__ uint32_t part[SLICE_ROWS][SLICE_THREADS / 64];
     const uint32_t base = blockIdx.x * SLICE_CHUNK + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    NodeRec ahead = slice_record(nodes, n, base);
+    NodeRec ahead = cell_record(nodes, n, base);
     uint32_t run = chunk[blockIdx.x];                           // the first record of this row's first wave
 #pragma unroll 1
     for (int row = 0; row < SLICE_ROWS; row++) {
         const uint32_t i = base + (uint32_t)row * SLICE_THREADS;
         const NodeRec rec = ahead;
-        if (row + 1 < SLICE_ROWS) ahead = slice_record(nodes, n, i + SLICE_THREADS);
+        if (row + 1 < SLICE_ROWS) ahead = cell_record(nodes, n, i + SLICE_THREADS);
         const uint32_t in8 = inside_bits(rec.z, rec.w);
         const SliceNode s = slice_node<false>(nodes, n, i, rec, level, in8);
         const float S = __int_as_float((127 - s.depth) << 23);
         uint32_t k0 = 0, k1 = 0, cnt = 0;
         if (s.cut && candidate_layers(pl, s.cx, s.cy, s.cz, S, k0, k1))
             cnt = slice_cell<false>(pl, rec.z, rec.w, in8, s.cx, s.cy, s.cz, S, k0, k1, i, 0u, nullptr, nullptr);
-        const uint32_t incl = slice_wave_scan(cnt);
+        const uint32_t incl = wave_scan(cnt);
         if (lane == 63u) part[row][wave] = incl;
         __syncthreads();
-        uint32_t first = run + incl - cnt;
-#pragma unroll
-        for (uint32_t w = 0; w < SLICE_THREADS / 64; w++) {
-            if (w < wave) first += part[row][w];
-            run += part[row][w];
-        }
+        const uint32_t first = ordered_first(incl, cnt, part[row], wave, run);
         if (cnt) slice_cell<true>(pl, rec.z, rec.w, in8, s.cx, s.cy, s.cz, S, k0, k1, i, first, out, nullptr);
     }
 }

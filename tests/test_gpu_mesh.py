@@ -1,13 +1,14 @@
 """Surface extraction on the GPU (sdfhip_scene_mesh / sdfhip_scene_mesh_device), both flavours of the library: every float of every
 vertex is the numpy restatement's (tests/mesh_restatement.py, held to the pinned counts and the frozen oracle by tests/test_mesh.py)
-bit for bit, NaN equal to NaN, on analytic trees, a depth-10 builder tree, a carved tree with cells of mixed depth and the 28 M-node
-scene, at levels from the root to deeper than the tree; the _device form counts, fills, refuses a short buffer and leaves frames in
+bit for bit, NaN equal to NaN, on analytic trees, a depth-10 builder tree, a carved tree with cells of mixed depth, a 1.4 M-node tree with
+more chunks than the chunk scan has threads and the 28 M-node scene, at levels from the root to deeper than the tree; the _device form counts, fills, refuses a short buffer and leaves frames in
 flight alone; the errors are status codes; a mesh goes back through the builder."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import big_cell_tree
 import edit_restatement as er
 import mesh_restatement as mr
 from conftest import assert_frames_identical, make_camera
@@ -103,6 +104,19 @@ def test_mesh_is_the_restatements(sb, name, levels):
                 assert len(np.unique(walked[0][nodes])) >= 2    # cut cells of mixed depth
         assert scene.Mesh(0)[1].cells == 1
     assert total > 0
+
+
+def test_more_chunks_than_the_scan_has_threads(sb):
+    """each of the 1024 threads of the chunk scan (scan_device.h, the slice's too) owns more than one chunk's total"""
+    od = big_cell_tree.tree()
+    assert len(od.Structs) > 1024 * 1024
+    ref, _, (cells, cut) = big_cell_tree.meshed()
+    assert (od.Length, cells, cut, len(ref)) == (big_cell_tree.NODES, big_cell_tree.CELLS, big_cell_tree.CELLS_CUT, big_cell_tree.TRIANGLES)
+    with sb.Scene(od) as scene:
+        got, st = scene.Mesh(-1)
+        assert (st.nodes, st.cells, st.cells_cut, st.n_triangles) == (od.Length, cells, cut, len(ref))
+        assert_mesh(got, ref, "more chunks than scan threads")
+        assert scene.MeshDevice() == len(ref)
 
 
 @pytest.mark.parametrize("name", ["torus_d6", "carved_d7"])

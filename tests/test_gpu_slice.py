@@ -2,7 +2,8 @@
 record, the per-layer counts and the statistics are the numpy restatement's (tests/slice_restatement.py, which tests every triangle of
 the mesh restatement against every layer and is held to things it did not make by tests/test_slice.py) -- on the golden trees, a carved
 tree with cells of mixed depth and the zoo's trees round the 1024-node workgroup, for an axis stack, a stack on cell faces, an oblique
-stack, 257 layers that ALL lie on cell faces (the reject margin's worst case), 4096 layers over the 12-deep chain and 65 536 over one cell; the
+stack, 257 layers that ALL lie on cell faces (the reject margin's worst case), 4096 layers over the 12-deep chain and 65 536 over one cell, and on a
+1.4 M-node tree with more chunks than the chunk scan has threads; the
 _device form counts, fills, refuses a short buffer, writes the layer counts either way and leaves frames in flight alone; the errors
 are status codes; the records are the slice of Scene.Mesh's own triangles."""
 import ctypes
@@ -10,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import big_cell_tree
 import edit_restatement as er
 import mesh_restatement as mr
 import slice_restatement as sr
@@ -113,6 +115,23 @@ def test_slice_is_the_restatements(sb, name, levels, planes):
         got, starts = scene.Slice(*PLANES[planes[0]], levels[0], want_stats=False)              # no statistics: the other count kernel
         assert_records(got, sr.by_layer(restated(name, levels[0], planes[0])[0], PLANES[planes[0]][3])[0], (name, "no statistics"))
     assert total > 0
+
+
+def test_more_chunks_than_the_scan_has_threads(sb):
+    """each of the 1024 threads of the chunk scan (scan_device.h, the mesh's too) owns more than one chunk's total; the tree and its
+    restated triangles are big_cell_tree.py's, made once for both modules"""
+    od, triple = big_cell_tree.tree(), big_cell_tree.meshed()
+    assert len(od.Structs) > 1024 * 1024
+    plane = ((0.0, 0.0, 1.0), 0.1, 0.1, 9)
+    rec, counts, (cells, cut, crossed) = want(("slice", "big"), lambda: sr.slice_scene(od.Structs, od.Values, *plane, -1, meshed=triple))
+    assert (len(rec), crossed) == (9376, 2570)
+    ref, ref_starts = sr.by_layer(rec, plane[3])
+    with sb.Scene(od) as scene:
+        got, starts, st = scene.Slice(*plane, -1)
+        assert (st.nodes, st.cells, st.cells_cut, st.cells_crossed, st.n_segments) == (od.Length, cells, cut, crossed, len(rec))
+        assert starts.tolist() == ref_starts.tolist() and np.diff(starts).tolist() == counts.tolist()
+        assert_records(got, ref, "more chunks than scan threads")
+        assert scene.SliceDevice(normal=plane[0], offset=plane[1], pitch=plane[2], layers=plane[3], level=-1) == len(rec)
 
 
 def test_the_most_layers_there_may_be(sb):
