@@ -843,7 +843,11 @@ SDFHIP_API int sdfhip_scene_pick(sdfhip_scene *scene, const sdfhip_info *info, c
  * shader's fused operations fused as DESIGN.md section 3 has them):
  *   F(p)       sdfhip_scene_compose's fold, word for word: u_k(p) = sdfhip_scene_place's value of instances[k]; v = u_0; then in list
  *              order UNION v = fminf(v, u_k); INTERSECT v = fmaxf(v, u_k); SUBTRACT v = fmaxf(v, -u_k).  Every look-up starts at its
- *              source's root: no cursor is carried from step to step, F depends on the point alone
+ *              source's root: no cursor is carried from step to step, F depends on the point alone.  Here the value leaves as a
+ *              float, so the one case C leaves open is pinned: of two zeros of opposite sign fminf gives -0 and fmaxf +0, whichever
+ *              operand comes first (-0 orders below +0: IEEE 754-2019's minimumNumber / maximumNumber, and what gfx950's
+ *              v_min_f32 / v_max_f32 compute).  It is met: a source that reads +0 at p, joined and then subtracted, folds
+ *              fmaxf(+0, -0), and F(p) = +0
  *   w(p)       the winner, tracked beside the fold: w = 0; UNION: w = k iff u_k < v before the fold; INTERSECT: iff u_k > v; SUBTRACT:
  *              iff -u_k > v.  Ties keep the earlier instance
  *   G(p)       with h = normal_step: (F(p + (h,0,0)) - F(p - (h,0,0)), F(p + (0,h,0)) - F(p - (0,h,0)), F(p + (0,0,h)) - F(p - (0,0,h))),

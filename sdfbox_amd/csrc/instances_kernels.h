@@ -10,7 +10,9 @@
 // tests/instances_restatement.py restates it with numpy on compose_restatement.value.
 //   u_k(p)    place_value (place_kernels.h) of instance k's source under instance k's map, by the instance's cursor form
 //             (compose_instance_value): every look-up starts at the root, no cursor is carried, so F depends on the point alone
-//   F(p)      v = u_0; then in list order UNION fminf(v, u_k), INTERSECT fmaxf(v, u_k), SUBTRACT fmaxf(v, -u_k)
+//   F(p)      v = u_0; then in list order UNION fminf(v, u_k), INTERSECT fmaxf(v, u_k), SUBTRACT fmaxf(v, -u_k); of two zeros of
+//             opposite sign fminf is -0 and fmaxf +0 (the header pins it: v_min_f32 / v_max_f32 order -0 below +0, and the MI355X
+//             returns +0 for fmaxf(+0, -0), tests/test_gpu_instances_zoo.py's "signtie")
 //   w(p)      w = 0; UNION: w = k iff u_k < v before the fold; INTERSECT: iff u_k > v; SUBTRACT: iff -u_k > v (ties keep the earlier)
 //   G(p)      (F(p + (h,0,0)) - F(p - (h,0,0)), F(p + (0,h,0)) - F(p - (0,h,0)), F(p + (0,0,h)) - F(p - (0,0,h))), h = normal_step;
 //             the offsets are added as vectors: the other two coordinates are p_a + 0.0f and p_a - 0.0f

@@ -100,14 +100,14 @@ def limit_parts(n):
 
 def folded_value(instances, p):
     """compose_restatement.value by another route: plr.value once per DISTINCT (source, placement) of the list, then the fold over
-    the whole list in list order with np.fmin / np.fmax.  The same floats in the same order of operations: the same bits."""
+    the whole list in list order with cr.fminf / cr.fmaxf.  The same floats in the same order of operations: the same bits."""
     seen, v = {}, None
     for src, (R, s, t), op in instances:
         key = (src[0].ctypes.data, src[1].ctypes.data, R.tobytes(), s.tobytes(), t.tobytes())
         if key not in seen:
             seen[key] = plr.value(src, p, R, s, t)
         u = seen[key]
-        v = u if v is None else np.fmin(v, u) if op == U else np.fmax(v, u) if op == I else np.fmax(v, -u)
+        v = u if v is None else cr.fminf(v, u) if op == U else cr.fmaxf(v, u) if op == I else cr.fmaxf(v, -u)
     return v
 
 

@@ -1,6 +1,6 @@
 """CPU restatement of sdfhip_scene_compose (include/sdfhip.h), numpy, float32 throughout, every operation an
 array operation of its own in the order the header writes it.  The value of one instance is place_restatement.value -- the placement
-is not restated here -- the fold is np.fmin / np.fmax in list order, and the construct rule and the node order are the ones
+is not restated here -- the fold is fminf / fmaxf (np.fmin / np.fmax, -0 below +0) in list order, and the construct rule and the node order are the ones
 place_restatement.place runs (from_float, CORNER, breadth first): the contracts cannot drift.  Every distinct point of a level is
 evaluated once against every instance (np.unique, as place_restatement.node_values does): a point's value depends on the point alone.
 
@@ -33,19 +33,38 @@ def as_instances(parts):
     return out
 
 
+def fminf(a, b):
+    """fminf as the header pins it (sdfhip_instances_*, F(p)): np.fmin, and of two zeros of opposite sign -0 whichever comes first
+    (np.fmin returns its second operand there).  No byte of a composition sees the difference: from_float does not see a zero's sign"""
+    r = np.fmin(a, b)
+    zero = r == 0                                   # (a tie of zeros can only be where the result is one: a long list folds fast)
+    if zero.any():
+        r = np.where(zero & (a == 0) & (b == 0) & (np.signbit(a) | np.signbit(b)), f32(-0.0), r)
+    return r
+
+
+def fmaxf(a, b):
+    """fmaxf as the header pins it: np.fmax, and of two zeros of opposite sign +0 whichever comes first"""
+    r = np.fmax(a, b)
+    zero = r == 0
+    if zero.any():
+        r = np.where(zero & (a == 0) & (b == 0) & ~(np.signbit(a) & np.signbit(b)), f32(0.0), r)
+    return r
+
+
 def value(instances, p):
-    """v(p) of the rule for points p (n, 3), float32: v = u_0, then in list order fmin(v, u_k), fmax(v, u_k) or fmax(v, -u_k)"""
+    """v(p) of the rule for points p (n, 3), float32: v = u_0, then in list order fminf(v, u_k), fmaxf(v, u_k) or fmaxf(v, -u_k)"""
     v = None
     for src, (R, s, t), op in instances:
         u = plr.value(src, p, R, s, t)
         if v is None:
             v = u
         elif op == COMBINE_UNION:
-            v = np.fmin(v, u)
+            v = fminf(v, u)
         elif op == COMBINE_INTERSECT:
-            v = np.fmax(v, u)
+            v = fmaxf(v, u)
         else:
-            v = np.fmax(v, -u)
+            v = fmaxf(v, -u)
     assert v.dtype == f32
     return v
 

@@ -61,7 +61,12 @@ def instances(name):
 
 def camera(name):
     """the case's camera, a Logic"""
-    cam_name, (W, H) = CASES[name][1], CASES[name][2]
+    return camera_named(CASES[name][1], CASES[name][2])
+
+
+def camera_named(cam_name, size):
+    """a camera of conftest.CAMERAS, or "inside", for a frame of `size` = (width, height)"""
+    W, H = size
     if cam_name == "inside":
         cam = make_camera("default", W, H)
         cam.Position = (0.5, 0.5, 0.45)            # inside the sphere of radius 0.3 round the cube's centre
@@ -89,7 +94,11 @@ def points(name):
 
 def pixels(name):
     """(n, 2) {x, y}: every fifth pixel of every fourth row, and the frame's corners"""
-    W, H = size(name)
+    return pixels_of(size(name))
+
+
+def pixels_of(size):
+    W, H = size
     xs, ys = np.meshgrid(np.arange(0, W, 5), np.arange(0, H, 4))
     px = np.stack([xs.ravel(), ys.ravel()], 1)
     return np.concatenate([px, [[0, 0], [W - 1, 0], [0, H - 1], [W - 1, H - 1]]]).astype(np.uint32)

@@ -7,7 +7,8 @@ find + interpol_world and gradient().  The camera ray, fma, dot and normalize ar
 so lanes are evaluated only while they are in a loop and the winner of a march is looked up once, at the last point it evaluated.
 
 tests/test_instances.py holds this file to things it did not come from; tests/test_gpu_instances.py holds the GPU to this file, bit
-for bit."""
+for bit, and tests/test_gpu_instances_zoo.py does on the tree zoo and at the calls' edges (a tie of signed zeros among them: the fold
+is compose_restatement's fminf / fmaxf, which order -0 below +0 as the header pins it)."""
 import numpy as np
 
 import compose_restatement as cr
@@ -26,7 +27,16 @@ PART_HIT = np.dtype({"names": ["position", "t", "normal", "prox", "status", "ste
                      "formats": [("<f4", (3,)), "<f4", ("<f4", (3,)), "<f4", "<u4", "<u4", "<u4", "<u4"],
                      "offsets": [0, 12, 16, 28, 32, 36, 40, 44], "itemsize": 48})
 
-value = cr.value          # F(p)
+
+class Folded(list):
+    """Instances of a list so long that few distinct (source, placement) pairs repeat in it (compose_cases.limit_parts): u_k is
+    evaluated once per distinct pair, and the value and the winner are folded over the whole list in list order -- the same floats
+    in the same order of operations, so the same bits (tests/test_instances_zoo.py holds the route to the plain one)."""
+
+
+def value(instances, p):
+    """F(p): compose_restatement.value; of a Folded list, the fold that winner() runs"""
+    return winner(instances, p)[1] if isinstance(instances, Folded) else cr.value(instances, p)
 
 
 def _finite(v):
@@ -37,18 +47,25 @@ def winner(instances, p):
     """(w(p), v(p)) for points p (n, 3): w = 0; UNION w = k iff u_k < v before the fold, INTERSECT iff u_k > v, SUBTRACT iff -u_k > v"""
     p = np.asarray(p, f32).reshape(-1, 3)
     v, w = None, np.zeros(len(p), np.int64)
+    seen = {} if isinstance(instances, Folded) else None
     with np.errstate(all="ignore"):
         for k, (src, (R, s, t), op) in enumerate(instances):
-            u = plr.value(src, p, R, s, t)
+            if seen is None:
+                u = plr.value(src, p, R, s, t)
+            else:
+                key = (src[0].ctypes.data, src[1].ctypes.data, R.tobytes(), s.tobytes(), t.tobytes())
+                if key not in seen:
+                    seen[key] = plr.value(src, p, R, s, t)
+                u = seen[key]
             if v is None:
                 v = u
             elif op == cr.COMBINE_UNION:
-                w = np.where(u < v, k, w); v = np.fmin(v, u)
+                w = np.where(u < v, k, w); v = cr.fminf(v, u)
             elif op == cr.COMBINE_INTERSECT:
-                w = np.where(u > v, k, w); v = np.fmax(v, u)
+                w = np.where(u > v, k, w); v = cr.fmaxf(v, u)
             else:
                 nu = -u
-                w = np.where(nu > v, k, w); v = np.fmax(v, nu)
+                w = np.where(nu > v, k, w); v = cr.fmaxf(v, nu)
     return w, v
 
 

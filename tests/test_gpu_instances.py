@@ -2,7 +2,8 @@
 tests/instances_cases.py through sample, raycast, pick and render is the CPU restatement's (tests/instances_restatement.py) bit for
 bit -- floats as their uint32 views; a NaN equals a NaN whatever its sign and payload, the project's convention (conftest.bits_equal,
 query_restatement.records_differ): numpy on the host and the GPU need not agree on the sign of a default NaN, and the only NaNs
-here are normals of a zero gradient, 0 * inf -- the host and the _device forms give the same bytes, so do the exact skip on and off
+in this file are normals of a zero gradient, 0 * inf (tests/test_gpu_instances_zoo.py meets others: gradients of far points, inf - inf)
+-- the host and the _device forms give the same bytes, so do the exact skip on and off
 and the sources' three cursor forms in every pairing; the sources are untouched and may be freed; the errors are status codes that
 name the instance; an allocation that fails is SDFHIP_ERR_NOMEM; the C++ mirror's methods give the same bytes."""
 import ctypes

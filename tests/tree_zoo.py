@@ -1,11 +1,14 @@
 """Trees built to break a consumer, shared by the tests of the renderer, the queries, the mesh, the edit, the prune, the combination,
-the placement, the measure, the volume read-out and the composition.  A plain helper module
+the placement, the measure, the volume read-out, the composition and the unbaked assembly calls.  A plain helper module
 (like the *_restatement.py files): generators of consistent trees that no builder would lay out -- depth-first order, a chain along
 one corner, blocks appended under randomly chosen leaves, node counts one past a kernel's chunk, row and wave -- byte fillers that are
 no distance field, the named trees `zoo()` every zoo test uses, the edit cases of tests/test_tree_zoo.py and
 tests/test_gpu_tree_zoo.py, the prune, combine, place and measure cases of tests/test_zoo_builders.py and
 tests/test_gpu_zoo_builders.py, and the volume-out and compose cases of tests/test_zoo_volumes.py and tests/test_gpu_zoo_volumes.py,
-with a cache of their restated results.
+with a cache of their restated results.  The assemblies of zoo trees that sdfhip_instances_* sample, march and draw without baking --
+each tree under the identity, the list `keeps`, the skip's floor, ties, the instance limit, the launch edges -- live in
+tests/instances_zoo_cases.py (tests/test_instances_zoo.py, tests/test_gpu_instances_zoo.py), which takes zoo(), compose_parts(),
+DEEP_CORNER and restated() from here.
 
 The volume-out and compose cases, and what each is for (measured CPU time of the restated answer beside it):
   out_lattices()    every tree of ALL_TREES, chain14 included, on a depth-3 tree's lattice, one that sticks out of the cube on every
