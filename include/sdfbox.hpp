@@ -300,6 +300,20 @@ public:
         Check(sdfhip_instances_sample(list.data(), (uint32_t)list.size(), opt, xyz.data(), (uint32_t)out.size(), out.data()));
         return out;
     }
+    // The clash check (sdfhip_instances_clash; nothing in the reference corresponds): which pairs of the parts share points of the
+    // lattice of 8^depth cell centres of the cube (opt: depth, origin, side, SDFHIP_CLASH_NO_SKIP; null = depth 6 on the unit cube),
+    // at most SDFHIP_CLASH_MAX_INSTANCES parts, the ops ignored.  One record per overlapping pair a < b, in (a, b) order: points,
+    // first, lo / hi, sum -- integers, the same bytes on every call.  stats (may be null).  No Program's model is touched
+    static std::vector<sdfhip_clash> ClashParts(const std::vector<Part> &parts, const sdfhip_clash_options *opt = nullptr,
+                                                sdfhip_clash_stats *stats = nullptr)
+    {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "ClashParts");
+        std::vector<sdfhip_clash> out(list.size() * (list.size() ? list.size() - 1 : 0) / 2);
+        uint32_t n = 0;
+        Check(sdfhip_instances_clash(list.data(), (uint32_t)list.size(), opt, out.empty() ? nullptr : out.data(), (uint32_t)out.size(), &n, stats));
+        out.resize(n);
+        return out;
+    }
     // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
     // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at
     // index (k * ny + j) * nx + i and at origin + (i, j, k) * spacing in the unit cube's coordinates, stored value * value_scale =

@@ -29,4 +29,22 @@ __device__ __forceinline__ float compose_instance_value(const ComposeInstance &I
     }
 }
 
+// The exact lower bound of u_k that needs no look-up (the argument: instances_kernels.h, "The exact skip"), shared by the assembly's
+// consumers (instances_kernels.h) and the clash check (clash_kernels.h)
+constexpr float INSTANCES_SKIP_FLOOR = -0.5625f;
+
+// b_k(p) = (-0.5625f + e) * s: place_value's lines up to e, word for word
+__device__ __forceinline__ float place_lower_bound(const PlaceMap &M, float px, float py, float pz)
+{
+    const float d0 = px - M.tx, d1 = py - M.ty, d2 = pz - M.tz;
+    const float qx = ((M.r[0][0] * d0 + M.r[1][0] * d1) + M.r[2][0] * d2) * M.inv;
+    const float qy = ((M.r[0][1] * d0 + M.r[1][1] * d1) + M.r[2][1] * d2) * M.inv;
+    const float qz = ((M.r[0][2] * d0 + M.r[1][2] * d1) + M.r[2][2] * d2) * M.inv;
+    const float cx = __builtin_fminf(__builtin_fmaxf(qx, 0.0f), 1.0f);
+    const float cy = __builtin_fminf(__builtin_fmaxf(qy, 0.0f), 1.0f);
+    const float cz = __builtin_fminf(__builtin_fmaxf(qz, 0.0f), 1.0f);
+    const float ex = qx - cx, ey = qy - cy, ez = qz - cz;
+    return (INSTANCES_SKIP_FLOOR + sqrtf((ex * ex + ey * ey) + ez * ez)) * M.s;
+}
+
 }  // namespace sdfhip

@@ -40,12 +40,11 @@
 // bound, the table index and each instance's op and form are the same for every lane -- and the table is read through a uniform
 // index; lanes diverge on the skip only.  G is a loop over its six taps round ONE inlined F, not six copies of it.
 #pragma once
-#include "compose_instance.h"   // ComposeInstance, compose_instance_value; place_kernels.h, query_kernels.h, raymarch_device.h
+#include "compose_instance.h"   // ComposeInstance, compose_instance_value, place_lower_bound; place_kernels.h, query_kernels.h, raymarch_device.h
 
 namespace sdfhip {
 
 constexpr int INSTANCES_THREADS = 256;
-constexpr float INSTANCES_SKIP_FLOOR = -0.5625f;
 
 // the call's assembly as a kernel reads it
 struct PartField {
@@ -54,20 +53,6 @@ struct PartField {
     uint32_t skip;          // 0: every instance is looked up at every point (SDFHIP_INSTANCES_NO_SKIP)
     float h;                // normal_step
 };
-
-// b_k(p) = (-0.5625f + e) * s: place_value's lines up to e, word for word
-__device__ __forceinline__ float place_lower_bound(const PlaceMap &M, float px, float py, float pz)
-{
-    const float d0 = px - M.tx, d1 = py - M.ty, d2 = pz - M.tz;
-    const float qx = ((M.r[0][0] * d0 + M.r[1][0] * d1) + M.r[2][0] * d2) * M.inv;
-    const float qy = ((M.r[0][1] * d0 + M.r[1][1] * d1) + M.r[2][1] * d2) * M.inv;
-    const float qz = ((M.r[0][2] * d0 + M.r[1][2] * d1) + M.r[2][2] * d2) * M.inv;
-    const float cx = __builtin_fminf(__builtin_fmaxf(qx, 0.0f), 1.0f);
-    const float cy = __builtin_fminf(__builtin_fmaxf(qy, 0.0f), 1.0f);
-    const float cz = __builtin_fminf(__builtin_fmaxf(qz, 0.0f), 1.0f);
-    const float ex = qx - cx, ey = qy - cy, ez = qz - cz;
-    return (INSTANCES_SKIP_FLOOR + sqrtf((ex * ex + ey * ey) + ez * ez)) * M.s;
-}
 
 // F(p), and w(p) beside it
 __device__ __forceinline__ float part_field(const PartField &A, float px, float py, float pz, uint32_t &w)

@@ -147,6 +147,27 @@ def lattice_of_depth(d):
     return ((2 ** d + 1,) * 3, (0, 0, 0), 2.0 ** -d)
 
 
+def clash_volume(rec, depth, side=1.0):
+    """The volume of a clash record's overlap on the lattice of Scene.ClashParts(depth=depth, side=side): points * pitch^3."""
+    return int(rec["points"]) * (float(side) * 2.0 ** -int(depth)) ** 3
+
+
+def clash_centroid(rec, depth, origin=(0.0, 0.0, 0.0), side=1.0):
+    """The centroid (3,) of a clash record's shared lattice points: origin + (sum / points + 0.5) * pitch."""
+    pitch = float(side) * 2.0 ** -int(depth)
+    return np.asarray(origin, dtype=np.float64) + (np.asarray(rec["sum"], dtype=np.float64) / float(rec["points"]) + 0.5) * pitch
+
+
+def clash_box(rec, depth, origin=(0.0, 0.0, 0.0), side=1.0):
+    """(origin, side) of the smallest cube round the cells lo..hi of a clash record, centred on them: the arguments of a second
+    Scene.ClashParts that looks at this clash again at a finer pitch."""
+    pitch = float(side) * 2.0 ** -int(depth)
+    lo, hi = np.asarray(rec["lo"], dtype=np.float64), np.asarray(rec["hi"], dtype=np.float64) + 1.0
+    cube = float((hi - lo).max()) * pitch
+    centre = np.asarray(origin, dtype=np.float64) + (lo + hi) * 0.5 * pitch
+    return tuple(float(c) for c in centre - cube * 0.5), cube
+
+
 class Scene:
     """A scene resident in one GPU's HBM (replaces the `data` / `values`
     bindings of Program.cs:147-152)."""
@@ -374,6 +395,22 @@ class Scene:
                                                  ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(stream)) if stream else None))
 
     # -- volumes in and out (sdfhip_volume_build / sdfhip_scene_volume): a dense lattice of distances as a scene and back -------------
+    @staticmethod
+    def ClashParts(parts, depth=6, origin=(0.0, 0.0, 0.0), side=1.0, skip=True):
+        """The clash check (sdfhip_instances_clash): which pairs of the parts overlap on the lattice of the 8^depth cell centres of the
+        cube (origin, side), depth 0..10.  parts: what Compose takes, at most CLASH_MAX_INSTANCES of them; the ops are ignored, every
+        part counts as a solid.  Returns (records, stats): a structured array of sdfhip_clash records in (a, b) order -- a < b, points =
+        the lattice points inside both, first = the lowest linear index (z << 2 depth | y << depth | x) among them, lo / hi their
+        inclusive lattice bounds, sum the sums of their x, y and z -- and a ClashStats.  Everything is an integer: two calls give the
+        same bytes.  clash_volume(), clash_centroid() and clash_box() read a record.  Nothing is built and nothing is kept."""
+        _, arr = Scene._instances("ClashParts", parts)
+        opt = _lib.ClashOptions(0 if skip else _lib.CLASH_NO_SKIP, depth, np.asarray(origin, dtype=np.float32).reshape(3).tolist(), side)
+        st = _lib.ClashStats()
+        n = ctypes.c_uint32()
+        out = np.zeros(len(arr) * (len(arr) - 1) // 2, dtype=np.dtype(_lib.Clash))
+        check(lib.sdfhip_instances_clash(arr, len(arr), ctypes.byref(opt), out.ctypes.data if len(out) else None, len(out), ctypes.byref(n), ctypes.byref(st)))
+        return out[:n.value].copy(), st
+
     @classmethod
     def FromVolume(cls, grid, origin=(0, 0, 0), spacing=None, depth=None, value_scale=1.0, device=0, want_octdata=False, want_stats=False):
         """A scene from a regular lattice of distances (sdfhip_volume_build[_device]): `grid` is a C-contiguous (nz, ny, nx) numpy
