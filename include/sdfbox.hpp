@@ -314,6 +314,25 @@ public:
         out.resize(n);
         return out;
     }
+    // The components of the loaded model (sdfhip_scene_components; nothing in the reference corresponds): its face-connected solids
+    // and voids on the lattice of 8^depth cell centres of the cube (opt: depth 0..9, origin, side; null = depth 6 on the unit cube).
+    // One record per component in ascending label order -- label = its lowest linear index, flags = SDFHIP_COMPONENT_SOLID or 0 for a
+    // void, points, lo / hi, sum: integers, the same bytes on every call.  labels (may be null): resized to 8^depth, every point's
+    // label in linear-index order.  stats (may be null).  The model is untouched
+    std::vector<sdfhip_component> Components(const sdfhip_components_options *opt = nullptr, std::vector<uint32_t> *labels = nullptr,
+                                             sdfhip_components_stats *stats = nullptr) const
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Components: no model loaded");
+        if (labels) labels->resize((size_t)1 << (3 * (opt && opt->depth <= SDFHIP_COMPONENTS_MAX_DEPTH ? opt->depth : 6u)));
+        std::vector<sdfhip_component> out(64);
+        for (;;) {
+            uint32_t n = 0;
+            Check(sdfhip_scene_components(scene, opt, out.data(), (uint32_t)out.size(), &n, labels ? labels->data() : nullptr, stats));
+            const bool all = n <= out.size();
+            out.resize(n);
+            if (all) return out;
+        }
+    }
     // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
     // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at
     // index (k * ny + j) * nx + i and at origin + (i, j, k) * spacing in the unit cube's coordinates, stored value * value_scale =

@@ -52,12 +52,14 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 INSTANCES_NO_SKIP = 1                # sdfhip_instances_options.flags: look every instance up at every point
 CLASH_NO_SKIP = 1                    # sdfhip_clash_options.flags: look every instance up at every lattice point
 CLASH_MAX_INSTANCES = 64             # sdfhip_instances_clash: a containment mask is one 64-bit word
+COMPONENT_SOLID = 1                  # sdfhip_component.flags: a component of the inside phase (0: a void)
+COMPONENTS_MAX_DEPTH = 9             # sdfhip_scene_components: 4 bytes per lattice point
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, ComponentsOptions, Component, ComponentsStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -401,6 +403,32 @@ else:
     assert (ctypes.sizeof(ClashOptions), ctypes.sizeof(Clash), ctypes.sizeof(ClashStats)) == (28, 64, 32)
 
 
+    class ComponentsOptions(ctypes.Structure):
+        """sdfhip_components_options: flags 0; depth 0..9 (2^depth lattice points along each axis); the cube's origin and side
+        (finite, above 0)."""
+        _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("depth", ctypes.c_uint32), ("origin", ctypes.c_float * 3),
+                    ("side", ctypes.c_float)]
+
+        def __init__(self, flags=0, depth=6, origin=(0.0, 0.0, 0.0), side=1.0):
+            super().__init__(ctypes.sizeof(type(self)), int(flags), int(depth), (ctypes.c_float * 3)(*[float(x) for x in origin]), float(side))
+
+
+    class Component(ctypes.Structure):
+        """sdfhip_component: one face-connected component of a scene on a lattice (sdfhip_scene_components); flags COMPONENT_SOLID for
+        the inside phase, 0 for a void."""
+        _fields_ = [("label", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("points", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                    ("lo", ctypes.c_uint32 * 3), ("hi", ctypes.c_uint32 * 3), ("sum", ctypes.c_uint64 * 3)]
+
+
+    class ComponentsStats(ctypes.Structure):
+        """sdfhip_components_stats: points = 8^depth, inside = those with value < 0, the records and the solids among them."""
+        _fields_ = [("points", ctypes.c_uint64), ("inside", ctypes.c_uint64), ("components", ctypes.c_uint32), ("solids", ctypes.c_uint32),
+                    ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(ComponentsOptions), ctypes.sizeof(Component), ctypes.sizeof(ComponentsStats)) == (28, 64, 32)
+
+
     class MeshOptions(ctypes.Structure):
         """sdfhip_mesh_options: level -1 = the leaves (full detail), 0..12 = the level-of-detail mesh of that level."""
         _fields_ = [("size", ctypes.c_uint32), ("level", ctypes.c_int32)]
@@ -607,6 +635,11 @@ _SIG = {
     "sdfhip_clash_options_default": (None, [_c.POINTER(ClashOptions)]),
     "sdfhip_instances_clash": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(ClashOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32),
                                           _c.POINTER(ClashStats)]),
+    "sdfhip_components_options_default": (None, [_c.POINTER(ComponentsOptions)]),
+    "sdfhip_scene_components": (_c.c_int, [_vp, _c.POINTER(ComponentsOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp,
+                                           _c.POINTER(ComponentsStats)]),
+    "sdfhip_scene_components_device": (_c.c_int, [_vp, _c.POINTER(ComponentsOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp,
+                                                  _c.POINTER(ComponentsStats)]),
     "sdfhip_mesh_options_default": (None, [_c.POINTER(MeshOptions)]),
     "sdfhip_scene_mesh": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _c.POINTER(CMesh), _c.POINTER(MeshStats)]),
     "sdfhip_scene_mesh_device": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp]),

@@ -37,6 +37,7 @@
 // The look-up counters go to CLASH_STAT_SLOTS slots by block number, so that a lattice of 2^18 blocks does not queue on one address.
 #pragma once
 #include "compose_instance.h"   // ComposeInstance, compose_instance_value, place_lower_bound; place_kernels.h, query_kernels.h
+#include "scan_device.h"        // block_axis (shared with components_kernels.h)
 
 namespace sdfhip {
 
@@ -80,21 +81,6 @@ __global__ __launch_bounds__(CLASH_THREADS) void k_clash_init(ClashPair *__restr
     P.a = a; P.b = b; P.points = 0u; P.first = 0xFFFFFFFFu;
     for (int k = 0; k < 3; k++) { P.lo[k] = 0xFFFFFFFFu; P.hi[k] = 0u; P.sum[k] = 0ull; }
     pairs[clash_pair_index(a, b, K)] = P;
-}
-
-// the lowest / highest j in 0..3 for which `both` meets base << (j * step), and the sum of j over the lanes of `both`
-__device__ __forceinline__ void clash_axis(unsigned long long both, unsigned long long base, int step, uint32_t &lo, uint32_t &hi, uint32_t &sum)
-{
-    lo = 3u; hi = 0u; sum = 0u;
-#pragma unroll
-    for (int j = 3; j >= 0; j--)
-        if (both & (base << (j * step))) lo = (uint32_t)j;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned long long m = both & (base << (j * step));
-        if (m) hi = (uint32_t)j;
-        sum += (uint32_t)j * (uint32_t)__popcll(m);
-    }
 }
 
 __global__ __launch_bounds__(CLASH_THREADS) void k_clash(const ComposeInstance *__restrict__ table, ClashLattice L, ClashPair *__restrict__ pairs,
@@ -149,9 +135,9 @@ __global__ __launch_bounds__(CLASH_THREADS) void k_clash(const ComposeInstance *
             if (!both) continue;
             const uint32_t n = (uint32_t)__popcll(both), low = (uint32_t)__ffsll((long long)both) - 1u;
             uint32_t lo[3], hi[3], sum[3];
-            clash_axis(both, 0x1111111111111111ull, 1, lo[0], hi[0], sum[0]);
-            clash_axis(both, 0x000F000F000F000Full, 4, lo[1], hi[1], sum[1]);
-            clash_axis(both, 0x000000000000FFFFull, 16, lo[2], hi[2], sum[2]);
+            block_axis(both, 0x1111111111111111ull, 1, lo[0], hi[0], sum[0]);
+            block_axis(both, 0x000F000F000F000Full, 4, lo[1], hi[1], sum[1]);
+            block_axis(both, 0x000000000000FFFFull, 16, lo[2], hi[2], sum[2]);
             if (lane == 0u) {
                 const uint32_t base[3] = {bx, by, bz};
                 const uint32_t first = ((bz + (low >> 4)) << (2u * d)) | ((by + ((low >> 2) & 3u)) << d) | (bx + (low & 3u));

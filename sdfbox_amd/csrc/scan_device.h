@@ -1,5 +1,6 @@
 // The workgroup scan and the bitmap rank that the tree rewriters share, and the chunk scan, the wave sums and the ordered offset of
-// the passes over a scene's cells (mesh, slice; the lane rank is the edit's and the prune's) (gfx950).  Everything here is a template or
+// the passes over a scene's cells (mesh, slice; the lane rank is the edit's and the prune's), and the axis sums of a wave that is a
+// block of a lattice (clash, components) (gfx950).  Everything here is a template or
 // __device__ __forceinline__, so any .hip may include it -- unlike the kernel headers (edit_kernels.h, prune_kernels.h, ...), whose
 // kernels are not templates and which are therefore included by one translation unit ONLY.  That rule stays: a kernel that is not a
 // template does not belong here.
@@ -106,6 +107,23 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v)
         if (lane >= (uint32_t)o) v += u;
     }
     return v;
+}
+
+// A wave that is a 4 x 4 x 4 block of a lattice, lane = lz * 16 + ly * 4 + lx (clash_kernels.h, components_kernels.h): of the lanes of
+// the ballot `both`, along the axis whose lanes with coordinate 0 are `base` and whose neighbours are `step` lanes apart, the lowest
+// / highest coordinate j in 0..3 and the sum of j -- scalar arithmetic on the one 64-bit word, no cross-lane reduction
+__device__ __forceinline__ void block_axis(unsigned long long both, unsigned long long base, int step, uint32_t &lo, uint32_t &hi, uint32_t &sum)
+{
+    lo = 3u; hi = 0u; sum = 0u;
+#pragma unroll
+    for (int j = 3; j >= 0; j--)
+        if (both & (base << (j * step))) lo = (uint32_t)j;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const unsigned long long m = both & (base << (j * step));
+        if (m) hi = (uint32_t)j;
+        sum += (uint32_t)j * (uint32_t)__popcll(m);
+    }
 }
 
 // The first output index of a lane that writes cnt records in lane order: incl = wave_scan(cnt); totals[w] = wave w's last incl, stored

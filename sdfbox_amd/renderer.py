@@ -168,6 +168,30 @@ def clash_box(rec, depth, origin=(0.0, 0.0, 0.0), side=1.0):
     return tuple(float(c) for c in centre - cube * 0.5), cube
 
 
+def component_volume(rec, depth, side=1.0):
+    """The volume of a component record on the lattice of Scene.Components(depth=depth, side=side): points * pitch^3."""
+    return int(rec["points"]) * (float(side) * 2.0 ** -int(depth)) ** 3
+
+
+def component_centroid(rec, depth, origin=(0.0, 0.0, 0.0), side=1.0):
+    """The centroid (3,) of a component's lattice points: origin + (sum / points + 0.5) * pitch."""
+    pitch = float(side) * 2.0 ** -int(depth)
+    return np.asarray(origin, dtype=np.float64) + (np.asarray(rec["sum"], dtype=np.float64) / float(rec["points"]) + 0.5) * pitch
+
+
+def component_box(rec, depth, origin=(0.0, 0.0, 0.0), side=1.0):
+    """(origin, side) of the smallest cube round the cells lo..hi of a component record, centred on them: the arguments of a second
+    Scene.Components that looks at this piece again at a finer pitch."""
+    return clash_box(rec, depth, origin, side)
+
+
+def component_enclosed(rec, depth):
+    """Does the component stay clear of the lattice's six faces (no lo == 0, no hi == 2^depth - 1)?  An enclosed void is a sealed
+    cavity."""
+    last = (1 << int(depth)) - 1
+    return bool(all(int(v) > 0 for v in rec["lo"]) and all(int(v) < last for v in rec["hi"]))
+
+
 class Scene:
     """A scene resident in one GPU's HBM (replaces the `data` / `values`
     bindings of Program.cs:147-152)."""
@@ -503,6 +527,41 @@ class Scene:
         check(lib.sdfhip_scene_volume_device(self._h, ctypes.byref(lattice), ctypes.c_void_p(out.data_ptr()),
                                              ctypes.c_void_p(int(stream)) if stream else None))
         return out
+
+    # -- components (sdfhip_scene_components[_device]): the separate solids and enclosed voids on a cubic lattice ------------------------
+    def _components(self, what, call, depth, origin, side, labels):
+        opt = _lib.ComponentsOptions(0, depth, np.asarray(origin, dtype=np.float32).reshape(3).tolist(), side)
+        st = _lib.ComponentsStats()
+        n = ctypes.c_uint32()
+        out = np.zeros(1024, dtype=np.dtype(_lib.Component))
+        # (a table of 1024 records holds all but a hostile scene's components; a longer one takes the call a second time)
+        for _ in range(2):
+            check(call(self._h, ctypes.byref(opt), out.ctypes.data, len(out), ctypes.byref(n), labels, ctypes.byref(st)))
+            if n.value <= len(out):
+                return out[:n.value].copy(), st
+            out = np.zeros(n.value, dtype=out.dtype)
+        raise RuntimeError(f"{what}: the number of components changed between two calls")
+
+    def Components(self, depth=6, origin=(0.0, 0.0, 0.0), side=1.0, labels=False):
+        """The face-connected components of this scene (sdfhip_scene_components) on the lattice of the 8^depth cell centres of the cube
+        (origin, side), depth 0..9: a point is inside iff the value Volume writes there is < 0, two points that differ by 1 in one
+        coordinate and are both inside or both outside are connected.  Returns (records, stats): a structured array of
+        sdfhip_component records in ascending label order -- label = the lowest linear index (z << 2 depth | y << depth | x) of the
+        component, flags = COMPONENT_SOLID for a solid and 0 for a void, points, lo / hi the inclusive lattice bounds, sum the sums
+        of x, y and z -- and a ComponentsStats.  labels=True: also every point's label, a uint32 array of shape (n, n, n), n = 2^depth,
+        indexed [z, y, x].  Everything is an integer: two calls give the same bytes.  component_volume(), component_centroid(),
+        component_box() and component_enclosed() read a record.  Nothing is built and nothing is kept."""
+        n = 1 << int(depth) if 0 <= int(depth) <= _lib.COMPONENTS_MAX_DEPTH else 1
+        lab = np.empty((n, n, n), dtype=np.uint32) if labels else None
+        rec, st = self._components("Components", lib.sdfhip_scene_components, depth, origin, side, lab.ctypes.data if labels else None)
+        return (rec, st, lab) if labels else (rec, st)
+
+    def ComponentsDevice(self, depth=6, origin=(0.0, 0.0, 0.0), side=1.0, labels_ptr=None):
+        """Components with the labels written to 8^depth uint32 words of device memory at `labels_ptr` on this scene's device (a torch
+        tensor's data_ptr(); None: no labels).  Synchronous, on a stream of the call's own: work enqueued on `labels_ptr` by other
+        streams must have been waited for.  Returns (records, stats), both in host memory."""
+        return self._components("ComponentsDevice", lib.sdfhip_scene_components_device, depth, origin, side,
+                                ctypes.c_void_p(int(labels_ptr)) if labels_ptr else None)
 
     # -- exact distance (sdfhip_scene_distance / _offset): clearance, offset and shell ------------------------------------------------
     def Distance(self, points, level=-1):
