@@ -333,6 +333,20 @@ public:
             if (all) return out;
         }
     }
+    // Selection (sdfhip_scene_select; nothing in the reference corresponds): the loaded model with some of its components' phases
+    // flipped -- a solid becomes empty space, a void becomes solid -- resampled into a new tree, which replaces the loaded model as
+    // Place's result does.  opt (null = the defaults: no rule, which is Place at the identity): the rule bits SDFHIP_SELECT_*, OR-ed,
+    // the components' lattice (lattice_depth 0..9, origin, side), the result's depth (-1 = the model's own) and min_points.  labels: the
+    // list of SDFHIP_SELECT_FLIP_LISTED or _KEEP_LISTED, labels as Components returns them on the same lattice, any order.  The removed
+    // pieces' former surfaces stay as structure; nothing is pruned.  host_out (may be null): the result's host arrays
+    void Select(const sdfhip_select_options *opt = nullptr, const std::vector<uint32_t> &labels = {}, sdfhip_select_stats *stats = nullptr,
+                sdfhip_octdata *host_out = nullptr)
+    {
+        if (!scene) throw Error(SDFHIP_ERR_ARG, "Select: no model loaded");
+        sdfhip_scene *fresh = nullptr;
+        Check(sdfhip_scene_select(scene, opt, labels.empty() ? nullptr : labels.data(), (uint32_t)labels.size(), &fresh, host_out, stats));
+        Adopt(fresh);
+    }
     // Volumes in and out (sdfhip_volume_build / sdfhip_scene_volume; nothing in the reference corresponds).  LoadVolume: the model
     // becomes the tree of at most `depth` levels (0..12) of a dense lattice of distances -- n = {nx, ny, nz} floats, sample (i, j, k) at
     // index (k * ny + j) * nx + i and at origin + (i, j, k) * spacing in the unit cube's coordinates, stored value * value_scale =

@@ -1064,6 +1064,80 @@ SDFHIP_API int sdfhip_scene_components_device(sdfhip_scene *scene, const sdfhip_
                                               uint32_t capacity, uint32_t *n_components, uint32_t *d_labels,
                                               sdfhip_components_stats *stats);
 
+/* ---- selection: keep, drop or fill a scene's components as a new scene --------------------------------------
+ * Replaces: nothing in the reference's code.  What to do with sdfhip_scene_components' answer: remove the crumbs a carve or a negative
+ * offset left behind, fill a sealed cavity before printing, keep the largest body of a scan, pull one body of a combination out as a
+ * scene of its own.  sdfhip_scene_select labels the scene as sdfhip_scene_components does, decides for every component whether its
+ * phase FLIPS (a solid becomes empty space, a void becomes solid), and resamples the scene into a NEW handle `*out` on the same
+ * device in which the flipped components have the other phase.  The source is read under its lock, stays untouched and may be freed
+ * as soon as the call returns.  The rule, pinned (fp32, each operation rounded on its own in the order written):
+ *   labelling  the lattice of opt (lattice_depth d, origin, side: sdfhip_components_options' cube, pitch = side * 2^-d) is labelled
+ *              exactly as sdfhip_scene_components labels it.  phase[i]: lattice point i is inside.  F[i]: i's component flips -- it
+ *              does if ANY rule bit of opt->flags flips it:
+ *                KEEP_LARGEST_SOLID   every solid but the one with most points (tie: the lowest label)
+ *                DROP_SMALL_SOLIDS    every solid with points < min_points
+ *                FILL_ENCLOSED_VOIDS  every void that is enclosed (no lo[a] == 0, no hi[a] == 2^d - 1)
+ *                FLIP_LISTED          the listed components, solid or void
+ *                KEEP_LISTED          every solid that is NOT listed
+ *              T[i] = phase[i] XOR F[i] is i's target phase
+ *   value      at a point p of the result's tree, v = sdfhip_scene_place's value at the identity (sdfhip_scene_components' value)
+ *   N(p)       per axis a: g = (p_a - origin_a) / pitch - 0.5f; f = floorf(g); the candidates are {f} if g == f, else {f, f + 1},
+ *              each clamped into 0 .. 2^d - 1 in float (fminf(fmaxf(., 0), 2^d - 1)) before it becomes an integer.  N(p) is the
+ *              product of the three sets: the lattice points with non-zero trilinear weight at p, 1 to 8 of them
+ *   classes    any: some point of N(p) has F; allin: every point of N(p) has T; allout: none has T
+ *   result     v' = -fmaxf(fabsf(v), h) if any && allin; v' = fmaxf(fabsf(v), h) if any && allout; v' = v otherwise.  h = 2^-8, a
+ *              constant: FromFloat(h, S) >= 64 for every S <= 1 while the surface sits at byte 63.75, so no corner of a zone that has
+ *              become empty reads as inside (with plain |v| every corner within 0.002 S of the former surface would be a speck); a
+ *              larger h would move kept surfaces that pass within a pitch of a removed piece
+ *   tree       sdfhip_scene_place's construct rule and node order on v': byte = FromFloat(v', S), a node splits iff
+ *              fabsf(v'(centre)) < 2 * S && d < depth; breadth first
+ * What the rule implies.  With no rule bit, or none that flips anything, v' = v everywhere: the result is sdfhip_scene_place at the
+ * identity, byte for byte.  At a result depth of at most 9 the links always equal the identity placement's: max(|v|, h) < 2 S iff
+ * |v| < 2 S while h < 2 S, which holds on levels 0..8, so only the bytes of nodes with a corner in a changed zone differ -- the removed
+ * piece's former surface stays resolved as ghost structure, and the distance bytes there are lower bounds, not distances:
+ * sdfhip_scene_offset by 0 re-distances the result and rebuilds the tree round the surviving surface alone.  Near-contacts: where a
+ * flipped piece lies within one pitch of a kept one of the same phase, N(p) is mixed and the point is left as it was; ask again on a
+ * finer lattice.  Cell centres only: features thinner than the pitch are not seen, as in sdfhip_scene_components.
+ * opt: NULL = the defaults (no rule); sdfhip_select_options_default sets them and the size, and the struct grows like
+ * sdfhip_components_options.  depth: the result's deepest level, -1 = the source's, else 0..12, as sdfhip_placement.depth.  labels /
+ * n_labels: the list of FLIP_LISTED or KEEP_LISTED -- component labels as sdfhip_scene_components returns them on the same lattice,
+ * in host memory, in any order, repeats allowed.  out, host_out: either may be NULL, not both, as sdfhip_scene_place's; on any
+ * failure *out is left as it was.  stats (may be NULL): the lattice's side -- components, solids, flipped_solids, flipped_voids,
+ * points_flipped (the lattice points of the flipped components) -- the tree's side as sdfhip_place_stats has it, and the times.
+ * SDFHIP_ERR_ARG before any device call: a null scene, both outputs NULL, a size the growth rule refuses, unknown flag bits, both
+ * FLIP_LISTED and KEEP_LISTED, a listed rule with n_labels == 0 or labels NULL, labels given without a listed rule, lattice_depth above
+ * 9, a non-finite origin, a side that is not finite or is <= 0 (or overflows origin + side), depth outside -1..12.  SDFHIP_ERR_ARG
+ * after the labelling pass, with nothing built and the label named in the message: a listed label that is not the label of a
+ * component (label >= 8^d or labels[label] != label), a void listed under KEEP_LISTED.  SDFHIP_ERR_BAD_TREE: depth -1 on a source that
+ * has no depth to give, as sdfhip_scene_place; SDFHIP_ERR_NOMEM, SDFHIP_ERR_DEVICE as elsewhere.  Device memory: the labelling's (4
+ * bytes per lattice point and the rest, freed before the tree is built), two bits per lattice point for F and T, then the
+ * placement's. */
+enum { SDFHIP_SELECT_KEEP_LARGEST_SOLID = 1,   /* flip every solid but the one with most points (tie: the lowest label) */
+       SDFHIP_SELECT_DROP_SMALL_SOLIDS  = 2,   /* flip every solid with points < min_points */
+       SDFHIP_SELECT_FILL_ENCLOSED_VOIDS = 4,  /* flip every void that is enclosed (no lo == 0, no hi == 2^d - 1) */
+       SDFHIP_SELECT_FLIP_LISTED = 8,          /* flip the listed components, solid or void */
+       SDFHIP_SELECT_KEEP_LISTED = 16 };       /* flip every solid that is NOT listed (a listed void: SDFHIP_ERR_ARG) */
+typedef struct sdfhip_select_options {
+    uint32_t size, flags;           /* sizeof(sdfhip_select_options) of the caller's header; rule bits, OR-ed: a component flips if any rule flips it */
+    uint32_t lattice_depth;         /* 0..9, the components' lattice */
+    float origin[3], side;          /* as sdfhip_components_options */
+    int32_t depth;                  /* the result's depth: -1 = the source's, else 0..12 (as sdfhip_placement.depth) */
+    uint32_t min_points;            /* DROP_SMALL_SOLIDS' threshold */
+} sdfhip_select_options;            /* 36 bytes */
+typedef struct sdfhip_select_stats { /* 64 bytes */
+    uint32_t components, solids;    /* the lattice's records; the solids among them */
+    uint32_t flipped_solids, flipped_voids;
+    uint64_t points_flipped;        /* the lattice points of the flipped components */
+    uint32_t nodes_in, nodes_out, depth_out, levels;    /* as sdfhip_place_stats */
+    uint64_t samples;               /* source look-ups made by the tree's levels: 9 for the root, 35 for every block of eight siblings */
+    float label_ms;                 /* HIP events around the labelling, the decision and the bitmaps */
+    float kernel_ms;                /* HIP events around the levels' kernels (the per-level host synchronisations included) */
+    float scene_ms, total_ms;       /* building the new handle; the whole call, host clock */
+} sdfhip_select_stats;
+SDFHIP_API void sdfhip_select_options_default(sdfhip_select_options *opt);   /* size, lattice depth 6, unit cube, depth -1, no rule */
+SDFHIP_API int sdfhip_scene_select(sdfhip_scene *scene, const sdfhip_select_options *opt, const uint32_t *labels, uint32_t n_labels,
+                                   sdfhip_scene **out, sdfhip_octdata *host_out, sdfhip_select_stats *stats);
+
 /* ---- surface extraction: a resident scene as triangles ------------------------------------------------
  * Replaces: nothing in the reference's code -- its tree only ever becomes pixels.  A scene that was built, carved and picked here
  * leaves as geometry: a triangle soup of 3 * n_triangles vertices of six floats {position, normal}, the layout of sdfhip_points.data,

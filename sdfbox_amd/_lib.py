@@ -54,12 +54,14 @@ CLASH_NO_SKIP = 1                    # sdfhip_clash_options.flags: look every in
 CLASH_MAX_INSTANCES = 64             # sdfhip_instances_clash: a containment mask is one 64-bit word
 COMPONENT_SOLID = 1                  # sdfhip_component.flags: a component of the inside phase (0: a void)
 COMPONENTS_MAX_DEPTH = 9             # sdfhip_scene_components: 4 bytes per lattice point
+# sdfhip_select_options.flags: the rule bits of sdfhip_scene_select, OR-ed
+SELECT_KEEP_LARGEST_SOLID, SELECT_DROP_SMALL_SOLIDS, SELECT_FILL_ENCLOSED_VOIDS, SELECT_FLIP_LISTED, SELECT_KEEP_LISTED = 1, 2, 4, 8, 16
 
 
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, ComponentsOptions, Component, ComponentsStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, ComponentsOptions, Component, ComponentsStats, SelectOptions, SelectStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -429,6 +431,28 @@ else:
     assert (ctypes.sizeof(ComponentsOptions), ctypes.sizeof(Component), ctypes.sizeof(ComponentsStats)) == (28, 64, 32)
 
 
+    class SelectOptions(ctypes.Structure):
+        """sdfhip_select_options: flags = SELECT_* rule bits, OR-ed; lattice_depth 0..9 and the cube's origin and side, as
+        ComponentsOptions; depth None = the source's depth, else 0..12; min_points: SELECT_DROP_SMALL_SOLIDS' threshold."""
+        _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("lattice_depth", ctypes.c_uint32), ("origin", ctypes.c_float * 3),
+                    ("side", ctypes.c_float), ("depth", ctypes.c_int32), ("min_points", ctypes.c_uint32)]
+
+        def __init__(self, flags=0, lattice_depth=6, origin=(0.0, 0.0, 0.0), side=1.0, depth=None, min_points=0):
+            super().__init__(ctypes.sizeof(type(self)), int(flags), int(lattice_depth), (ctypes.c_float * 3)(*[float(x) for x in origin]), float(side),
+                             -1 if depth is None else int(depth), int(min_points))
+
+
+    class SelectStats(ctypes.Structure):
+        """sdfhip_select_stats: the lattice's records and which of them flipped; the result's tree as PlaceStats has it; the times."""
+        _fields_ = [("components", ctypes.c_uint32), ("solids", ctypes.c_uint32), ("flipped_solids", ctypes.c_uint32),
+                    ("flipped_voids", ctypes.c_uint32), ("points_flipped", ctypes.c_uint64), ("nodes_in", ctypes.c_uint32),
+                    ("nodes_out", ctypes.c_uint32), ("depth_out", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("samples", ctypes.c_uint64),
+                    ("label_ms", ctypes.c_float), ("kernel_ms", ctypes.c_float), ("scene_ms", ctypes.c_float), ("total_ms", ctypes.c_float)]
+
+
+    assert (ctypes.sizeof(SelectOptions), ctypes.sizeof(SelectStats)) == (36, 64)
+
+
     class MeshOptions(ctypes.Structure):
         """sdfhip_mesh_options: level -1 = the leaves (full detail), 0..12 = the level-of-detail mesh of that level."""
         _fields_ = [("size", ctypes.c_uint32), ("level", ctypes.c_int32)]
@@ -640,6 +664,8 @@ _SIG = {
                                            _c.POINTER(ComponentsStats)]),
     "sdfhip_scene_components_device": (_c.c_int, [_vp, _c.POINTER(ComponentsOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp,
                                                   _c.POINTER(ComponentsStats)]),
+    "sdfhip_select_options_default": (None, [_c.POINTER(SelectOptions)]),
+    "sdfhip_scene_select": (_c.c_int, [_vp, _c.POINTER(SelectOptions), _vp, _c.c_uint32, _c.POINTER(_vp), _c.POINTER(COctData), _c.POINTER(SelectStats)]),
     "sdfhip_mesh_options_default": (None, [_c.POINTER(MeshOptions)]),
     "sdfhip_scene_mesh": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _c.POINTER(CMesh), _c.POINTER(MeshStats)]),
     "sdfhip_scene_mesh_device": (_c.c_int, [_vp, _c.POINTER(MeshOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp]),

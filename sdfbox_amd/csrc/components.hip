@@ -12,6 +12,9 @@
 // and -- after the one host synchronisation, whose count sizes the record table -- k_comp_init and k_comp_records fill the table.
 // Records, labels and counters come back in one copy each, after the last allocation: a call that runs out of memory has written
 // nothing.  Nothing is built and nothing is kept on the handle.
+//
+// The passes up to and including k_comp_records are label_components below, which sdfhip_scene_select (select.hip) calls too, with the
+// lattice's refusals (check_comp_lattice); components_host.h declares both.
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
 #include "components_kernels.h"
@@ -40,26 +43,12 @@ constexpr uint32_t RECORD_WAVES = 2048;                            // k_comp_rec
 int check_call(const char *name, const sdfhip_scene *scene, const sdfhip_components_options *opt, const sdfhip_component *out, uint32_t capacity,
                const uint32_t *n_components, CompLattice &L)
 {
-    float side = 1.0f;
-    L = CompLattice{0.0f, 0.0f, 0.0f, 0.0f, 6u, 0u};
+    const float unit[3] = {0.0f, 0.0f, 0.0f};
     if (opt) {
         if (const int rc = check_options_size(name, opt, sizeof(sdfhip_components_options), "sdfhip_components_options_default sets the size")) return rc;
         if (opt->flags) return fail(SDFHIP_ERR_ARG, "%s: unknown flags %#x", name, opt->flags);
-        if (opt->depth > SDFHIP_COMPONENTS_MAX_DEPTH)
-            return fail(SDFHIP_ERR_ARG, "%s: depth %u outside 0..%d (the call keeps 4 bytes per lattice point: 512 MB at depth 9, 4 GB at depth 10)", name,
-                        opt->depth, (int)SDFHIP_COMPONENTS_MAX_DEPTH);
-        if (!std::isfinite(opt->origin[0]) || !std::isfinite(opt->origin[1]) || !std::isfinite(opt->origin[2]))
-            return fail(SDFHIP_ERR_ARG, "%s: the origin (%g, %g, %g) is not finite", name, (double)opt->origin[0], (double)opt->origin[1], (double)opt->origin[2]);
-        if (!std::isfinite(opt->side) || !(opt->side > 0.0f)) return fail(SDFHIP_ERR_ARG, "%s: the side %g is not finite and above 0", name, (double)opt->side);
-        for (int a = 0; a < 3; a++)
-            if (!std::isfinite(opt->origin[a] + opt->side))
-                return fail(SDFHIP_ERR_ARG, "%s: the cube's far corner, origin + side = %g + %g, is not finite", name, (double)opt->origin[a], (double)opt->side);
-        L.ox = opt->origin[0]; L.oy = opt->origin[1]; L.oz = opt->origin[2];
-        L.depth = opt->depth;
-        side = opt->side;
     }
-    L.pitch = side * std::ldexp(1.0f, -(int)L.depth);
-    L.n_blocks = 1u << (3u * (L.depth > 2u ? L.depth - 2u : 0u));
+    if (const int rc = check_comp_lattice(name, "depth", opt ? opt->depth : 6u, opt ? opt->origin : unit, opt ? opt->side : 1.0f, L)) return rc;
     if (!n_components) return fail(SDFHIP_ERR_ARG, "%s: null n_components", name);
     if (!out && capacity > 0) return fail(SDFHIP_ERR_ARG, "%s: null out with capacity %u", name, capacity);
     if (!scene) return fail(SDFHIP_ERR_ARG, "%s: null scene", name);
@@ -74,54 +63,27 @@ int components(const char *name, sdfhip_scene *scene, const sdfhip_components_op
     CompLattice L;
     if (const int rc = check_call(name, scene, opt, out, capacity, n_components, L)) return rc;
     const Source src = read_source(scene);
-    const uint32_t n = 1u << (3u * L.depth), m = std::max(1u, n >> 5), nchunk = (m + 1023u) / 1024u;
-    const uint32_t per = COMP_THREADS / 64, by_block = (L.n_blocks + per - 1u) / per, by_point = (n + COMP_THREADS - 1u) / COMP_THREADS;
-    uint32_t total = 0;
+    CompLabels C;
     CompStat slots[COMP_STAT_SLOTS];
     float kernel_ms = 0.0f;
     CallFrame<2> call(name, src.device, FAIL_ALLOC, t0);
     const int rc = call.run("nothing was written", [&](hipStream_t st) -> int {
-        uint32_t *d_parent = call.bufs.get<uint32_t>(n);
-        unsigned long long *d_sign = call.bufs.get<unsigned long long>(L.n_blocks);
-        uint32_t *d_roots = call.bufs.get<uint32_t>(m + 1u);
-        uint32_t *d_pre = call.bufs.get<uint32_t>(m);
-        uint32_t *d_chunk = call.bufs.get<uint32_t>(nchunk + 1u);
-        CompStat *d_stats = call.bufs.get<CompStat>(COMP_STAT_SLOTS);
-        HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof slots, st));
-        HIP_TRY(hipEventRecord(call.cs.ev[0], st));
-        with_cursor(src.form, [&](auto c) {
-            hipLaunchKernelGGL((k_comp_local<typename decltype(c)::type>), dim3(by_block), dim3(COMP_THREADS), 0, st, src.Q, L, d_parent, d_sign, d_stats);
-        });
-        HIP_TRY(hipGetLastError());
-        if (L.n_blocks > 1u) hipLaunchKernelGGL(k_comp_merge, dim3(by_block), dim3(COMP_THREADS), 0, st, L, d_parent, d_sign);
-        hipLaunchKernelGGL(k_comp_flatten, dim3(by_point), dim3(COMP_THREADS), 0, st, d_parent, n, d_roots);
-        hipLaunchKernelGGL(k_rank_scan_words<CompRootWords>, dim3(nchunk), dim3(256), 0, st, CompRootWords{ d_roots }, m, d_pre, d_chunk);
-        hipLaunchKernelGGL(k_rank_scan_chunks<true>, dim3(1), dim3(1024), 0, st, d_chunk, nchunk);
-        HIP_TRY(hipGetLastError());
-        // the one host synchronisation: the count sizes the record table
-        HIP_TRY(hipMemcpyAsync(&total, d_chunk + nchunk, sizeof total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        Component *d_out = call.bufs.get<Component>(total);
-        hipLaunchKernelGGL(k_comp_init, dim3(by_point), dim3(COMP_THREADS), 0, st, L, n, d_roots, d_pre, d_chunk, d_sign, d_out, d_stats);
-        // (a run of blocks per wave: at most RECORD_WAVES waves flush the outer void's share)
-        const uint32_t run = (L.n_blocks + RECORD_WAVES - 1u) / RECORD_WAVES, waves = (L.n_blocks + run - 1u) / run;
-        hipLaunchKernelGGL(k_comp_records, dim3((waves + per - 1u) / per), dim3(COMP_THREADS), 0, st, L, run, d_parent, d_roots, d_pre, d_chunk, d_out);
-        HIP_TRY(hipGetLastError());
+        if (const int rc = label_components(call.bufs, st, src, L, call.cs.ev[0], C)) return rc;
         HIP_TRY(hipEventRecord(call.cs.ev[1], st));
         // (nothing is allocated from here on)
-        const uint32_t kept = std::min(capacity, total);
-        if (kept) HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)kept * sizeof(Component), hipMemcpyDeviceToHost, st));
-        if (labels) HIP_TRY(hipMemcpyAsync(labels, d_parent, (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(slots, d_stats, sizeof slots, hipMemcpyDeviceToHost, st));
+        const uint32_t kept = std::min(capacity, C.total);
+        if (kept) HIP_TRY(hipMemcpyAsync(out, C.d_out, (size_t)kept * sizeof(Component), hipMemcpyDeviceToHost, st));
+        if (labels) HIP_TRY(hipMemcpyAsync(labels, C.d_parent, (size_t)C.n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(slots, C.d_stats, sizeof slots, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return call.elapsed(&kernel_ms, 0, 1);
     });
     if (rc != SDFHIP_OK) return rc;
-    *n_components = total;
+    *n_components = C.total;
     if (stats) {
         memset(stats, 0, sizeof *stats);
-        stats->points = n;
-        stats->components = total;
+        stats->points = C.n;
+        stats->components = C.total;
         for (const CompStat &s : slots) { stats->inside += s.inside; stats->solids += s.solids; }
         stats->kernel_ms = kernel_ms;
         stats->total_ms = call.total_ms();
@@ -130,6 +92,62 @@ int components(const char *name, sdfhip_scene *scene, const sdfhip_components_op
 }
 
 }  // namespace
+
+// ---- what sdfhip_scene_select shares (components_host.h) --------------------------------------------------------------------------
+
+int sdfhip::check_comp_lattice(const char *name, const char *field, uint32_t depth, const float *origin, float side, CompLattice &L)
+{
+    if (depth > SDFHIP_COMPONENTS_MAX_DEPTH)
+        return fail(SDFHIP_ERR_ARG, "%s: %s %u outside 0..%d (the call keeps 4 bytes per lattice point: 512 MB at depth 9, 4 GB at depth 10)", name, field,
+                    depth, (int)SDFHIP_COMPONENTS_MAX_DEPTH);
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return fail(SDFHIP_ERR_ARG, "%s: the origin (%g, %g, %g) is not finite", name, (double)origin[0], (double)origin[1], (double)origin[2]);
+    if (!std::isfinite(side) || !(side > 0.0f)) return fail(SDFHIP_ERR_ARG, "%s: the side %g is not finite and above 0", name, (double)side);
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(origin[a] + side))
+            return fail(SDFHIP_ERR_ARG, "%s: the cube's far corner, origin + side = %g + %g, is not finite", name, (double)origin[a], (double)side);
+    L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
+    L.depth = depth;
+    L.pitch = side * std::ldexp(1.0f, -(int)depth);
+    L.n_blocks = 1u << (3u * (depth > 2u ? depth - 2u : 0u));
+    return SDFHIP_OK;
+}
+
+int sdfhip::label_components(DeviceBuffers &bufs, hipStream_t st, const Source &src, const CompLattice &L, hipEvent_t started, CompLabels &C)
+{
+    const uint32_t n = 1u << (3u * L.depth), m = std::max(1u, n >> 5), nchunk = (m + 1023u) / 1024u;
+    const uint32_t per = COMP_THREADS / 64, by_block = (L.n_blocks + per - 1u) / per, by_point = (n + COMP_THREADS - 1u) / COMP_THREADS;
+    C.n = n; C.m = m; C.nchunk = nchunk;
+    uint32_t *d_parent = C.d_parent = bufs.get<uint32_t>(n);
+    unsigned long long *d_sign = C.d_sign = bufs.get<unsigned long long>(L.n_blocks);
+    uint32_t *d_roots = C.d_roots = bufs.get<uint32_t>(m + 1u);
+    uint32_t *d_pre = C.d_pre = bufs.get<uint32_t>(m);
+    uint32_t *d_chunk = C.d_chunk = bufs.get<uint32_t>(nchunk + 1u);
+    CompStat *d_stats = C.d_stats = bufs.get<CompStat>(COMP_STAT_SLOTS);
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(CompStat) * COMP_STAT_SLOTS, st));
+    HIP_TRY(hipEventRecord(started, st));
+    with_cursor(src.form, [&](auto c) {
+        hipLaunchKernelGGL((k_comp_local<typename decltype(c)::type>), dim3(by_block), dim3(COMP_THREADS), 0, st, src.Q, L, d_parent, d_sign, d_stats);
+    });
+    HIP_TRY(hipGetLastError());
+    if (L.n_blocks > 1u) hipLaunchKernelGGL(k_comp_merge, dim3(by_block), dim3(COMP_THREADS), 0, st, L, d_parent, d_sign);
+    hipLaunchKernelGGL(k_comp_flatten, dim3(by_point), dim3(COMP_THREADS), 0, st, d_parent, n, d_roots);
+    hipLaunchKernelGGL(k_rank_scan_words<CompRootWords>, dim3(nchunk), dim3(256), 0, st, CompRootWords{ d_roots }, m, d_pre, d_chunk);
+    hipLaunchKernelGGL(k_rank_scan_chunks<true>, dim3(1), dim3(1024), 0, st, d_chunk, nchunk);
+    HIP_TRY(hipGetLastError());
+    // the one host synchronisation: the count sizes the record table
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_chunk + nchunk, sizeof total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    C.total = total;
+    Component *d_out = C.d_out = bufs.get<Component>(total);
+    hipLaunchKernelGGL(k_comp_init, dim3(by_point), dim3(COMP_THREADS), 0, st, L, n, d_roots, d_pre, d_chunk, d_sign, d_out, d_stats);
+    // (a run of blocks per wave: at most RECORD_WAVES waves flush the outer void's share)
+    const uint32_t run = (L.n_blocks + RECORD_WAVES - 1u) / RECORD_WAVES, waves = (L.n_blocks + run - 1u) / run;
+    hipLaunchKernelGGL(k_comp_records, dim3((waves + per - 1u) / per), dim3(COMP_THREADS), 0, st, L, run, d_parent, d_roots, d_pre, d_chunk, d_out);
+    HIP_TRY(hipGetLastError());
+    return SDFHIP_OK;
+}
 
 extern "C" void sdfhip_components_options_default(sdfhip_components_options *opt)
 try {

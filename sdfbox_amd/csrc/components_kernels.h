@@ -48,56 +48,18 @@
 //                    integer atomics when the wave leaves it.  A wave wholly inside one component issues one set for its whole run
 // No kernel uses scratch (profiles/components_kernel_resources.txt).
 #pragma once
-#include "query_kernels.h"   // QueryScene, grid_of; raymarch_device.h: the cursors, find_fresh, sample_after_find
+#include "components_host.h" // Component, CompStat, CompLattice, components_value (shared with select.hip); query_kernels.h: the cursors
 #include "scan_device.h"     // k_rank_scan_*, rank_in_bitmap, block_axis
 
 namespace sdfhip {
 
 constexpr int COMP_THREADS = 256;
-constexpr uint32_t COMP_STAT_SLOTS = 64, COMP_SOLID = 1u;
-
-// sdfhip_component of include/sdfhip.h
-struct Component {
-    uint32_t label, flags, points, reserved;
-    uint32_t lo[3], hi[3];
-    unsigned long long sum[3];
-};
-static_assert(sizeof(Component) == 64, "sdfhip_component of include/sdfhip.h");
-
-struct CompStat {
-    unsigned long long inside;
-    uint32_t solids, pad;
-};
-
-// the call's lattice as the kernels read it
-struct CompLattice {
-    float ox, oy, oz, pitch;
-    uint32_t depth;         // 0..9
-    uint32_t n_blocks;      // 8^max(depth - 2, 0)
-};
 
 // The root bitmap, words 0 .. m - 1, to k_rank_scan_words (scan_device.h)
 struct CompRootWords {
     const uint32_t *roots;
     __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return roots[i]; }
 };
-
-// value(p) of the rule: k_volume_out's lines (volume_kernels.h), word for word -- the clamp to the cube, the scene's distance there
-// (what sdfhip_scene_sample returns), continued outside at slope 1
-template <class CursorT> __device__ __forceinline__ float components_value(const QueryScene &Q, float px, float py, float pz)
-{
-    const float cx = __builtin_fminf(__builtin_fmaxf(px, 0.0f), 1.0f);
-    const float cy = __builtin_fminf(__builtin_fmaxf(py, 0.0f), 1.0f);
-    const float cz = __builtin_fminf(__builtin_fmaxf(pz, 0.0f), 1.0f);
-    const float ex = px - cx, ey = py - cy, ez = pz - cz;
-    CursorT c;
-    c.loads = 0;
-    c.reset(Q.nodes[0]);
-    typename CursorT::Pos u;
-    find_fresh(c, Q.nodes, grid_of(Q), Q.n_nodes, nullptr, 0u, cx, cy, cz, u);
-    const float D = sample_after_find(c, u, cx, cy, cz);
-    return D + sqrtf((ex * ex + ey * ey) + ez * ez);
-}
 
 // a wave's block and a lane's point in it
 struct CompPoint {

@@ -563,6 +563,56 @@ class Scene:
         return self._components("ComponentsDevice", lib.sdfhip_scene_components_device, depth, origin, side,
                                 ctypes.c_void_p(int(labels_ptr)) if labels_ptr else None)
 
+    # -- selection (sdfhip_scene_select): keep, drop or fill this scene's components as a new scene ------------------------------------
+    def Select(self, keep_largest=False, drop_below=0, fill_enclosed=False, flip=None, keep=None, lattice_depth=6, origin=(0.0, 0.0, 0.0),
+               side=1.0, depth=None, want_octdata=False, want_stats=False):
+        """Selection (sdfhip_scene_select): this scene with some of its components' phases flipped -- a solid becomes empty space, a
+        void becomes solid -- as a NEW Scene in breadth-first order on the same device; this one is left as it was.  The components
+        are those Components(lattice_depth, origin, side) reports.  A component flips if any rule flips it: keep_largest, every solid
+        but the one with most points (tie: the lowest label); drop_below=k > 0, every solid with fewer than k points; fill_enclosed,
+        every void that touches no face of the lattice; flip=[labels], the listed components, solid or void; keep=[labels], every
+        solid that is not listed (flip and keep exclude each other; a listed label must be a component's, and under keep a solid's).
+        With no rule the result is Place at the identity, byte for byte.  depth: None = this tree's depth, else 0..12.  The tree keeps
+        the removed pieces' former surfaces as structure (the bytes there are lower bounds): Offset(0) re-distances it; nothing is
+        pruned (chain Prune).  want_octdata: also the result's host arrays; want_stats: a SelectStats."""
+        if flip is not None and keep is not None:
+            raise ValueError("Select: flip and keep exclude each other")
+        flags = ((_lib.SELECT_KEEP_LARGEST_SOLID if keep_largest else 0) | (_lib.SELECT_DROP_SMALL_SOLIDS if int(drop_below) > 0 else 0)
+                 | (_lib.SELECT_FILL_ENCLOSED_VOIDS if fill_enclosed else 0) | (_lib.SELECT_FLIP_LISTED if flip is not None else 0)
+                 | (_lib.SELECT_KEEP_LISTED if keep is not None else 0))
+        listed = None if flip is None and keep is None else np.ascontiguousarray(flip if keep is None else keep, dtype=np.uint32).reshape(-1)
+        opt = _lib.SelectOptions(flags, lattice_depth, np.asarray(origin, dtype=np.float32).reshape(3).tolist(), side, depth, max(int(drop_below), 0))
+        where, count = (listed.ctypes.data if listed is not None and len(listed) else None), (0 if listed is None else len(listed))
+        return Scene._built(self.device, _lib.SelectStats(),
+                            lambda h, raw, st: lib.sdfhip_scene_select(self._h, ctypes.byref(opt), where, count, h, raw, st), want_octdata, want_stats)
+
+    def KeepLargest(self, lattice_depth=6, origin=(0.0, 0.0, 0.0), side=1.0, depth=None, want_octdata=False, want_stats=False):
+        """Select(keep_largest=True): this scene without its floating pieces."""
+        return self.Select(keep_largest=True, lattice_depth=lattice_depth, origin=origin, side=side, depth=depth, want_octdata=want_octdata,
+                           want_stats=want_stats)
+
+    def FillCavities(self, lattice_depth=6, origin=(0.0, 0.0, 0.0), side=1.0, depth=None, want_octdata=False, want_stats=False):
+        """Select(fill_enclosed=True): this scene with its sealed cavities filled."""
+        return self.Select(fill_enclosed=True, lattice_depth=lattice_depth, origin=origin, side=side, depth=depth, want_octdata=want_octdata,
+                           want_stats=want_stats)
+
+    def Split(self, lattice_depth=6, origin=(0.0, 0.0, 0.0), side=1.0, depth=None, max_parts=64):
+        """This scene's solids as scenes of their own: one Components call, then one Select(keep=[label]) per solid, in label order.
+        Returns the list of new Scenes (the caller closes them).  Raises ValueError when there are more solids than max_parts."""
+        rec, _ = self.Components(depth=lattice_depth, origin=origin, side=side)
+        solids = [int(r["label"]) for r in rec if r["flags"] & _lib.COMPONENT_SOLID]
+        if len(solids) > int(max_parts):
+            raise ValueError(f"Split: {len(solids)} solids, more than max_parts = {int(max_parts)}")
+        parts = []
+        try:
+            for label in solids:
+                parts.append(self.Select(keep=[label], lattice_depth=lattice_depth, origin=origin, side=side, depth=depth))
+        except Exception:
+            for p in parts:
+                p.close()
+            raise
+        return parts
+
     # -- exact distance (sdfhip_scene_distance / _offset): clearance, offset and shell ------------------------------------------------
     def Distance(self, points, level=-1):
         """The exact signed distance from points (n, 3) float32 to this scene's surface -- the triangles Mesh(level) emits -- at any
