@@ -314,6 +314,22 @@ public:
         out.resize(n);
         return out;
     }
+    // The penetration depth (sdfhip_instances_penetration; nothing in the reference corresponds): how far each overlapping pair of
+    // the parts reaches into the other, on ClashParts' lattice (opt: depth, origin, side, SDFHIP_PENETRATION_NO_SKIP; null = depth 6
+    // on the unit cube) and ClashParts' list.  One record per overlapping pair a < b, in (a, b) order: points, the witness, depth,
+    // ra / rb, the nearest cells and the nearest surface points of both parts -- the same bytes on every call.  stats (may be null).
+    // The workflow: ClashParts at a coarse depth, the cube round a record's lo..hi, this call on that cube.  No model is touched
+    static std::vector<sdfhip_penetration> PenetrationParts(const std::vector<Part> &parts, const sdfhip_penetration_options *opt = nullptr,
+                                                            sdfhip_penetration_stats *stats = nullptr)
+    {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "PenetrationParts");
+        std::vector<sdfhip_penetration> out(list.size() * (list.size() ? list.size() - 1 : 0) / 2);
+        uint32_t n = 0;
+        Check(sdfhip_instances_penetration(list.data(), (uint32_t)list.size(), opt, out.empty() ? nullptr : out.data(), (uint32_t)out.size(), &n,
+                                           stats));
+        out.resize(n);
+        return out;
+    }
     // The components of the loaded model (sdfhip_scene_components; nothing in the reference corresponds): its face-connected solids
     // and voids on the lattice of 8^depth cell centres of the cube (opt: depth 0..9, origin, side; null = depth 6 on the unit cube).
     // One record per component in ascending label order -- label = its lowest linear index, flags = SDFHIP_COMPONENT_SOLID or 0 for a

@@ -955,8 +955,9 @@ SDFHIP_API int sdfhip_instances_render_device(const sdfhip_instance *instances, 
  *   integers   everything in a record is an integer, accumulated with integer atomic add / min / max only; no float is ever summed:
  *              the bytes are the same on every call, whatever the waves' timing
  * No penetration depth.  The minimum over the overlap of max(u_a, u_b) saturates at the source's own band -- every pair of depth-4
- * spheres at half size gives -0.015625 -- because the stored field is a distance only near the surface.  A true depth needs
- * sdfhip_scene_distance's exact field and is not part of this call.
+ * spheres at half size gives -0.015625 -- because the stored field is a distance only near the surface.  The true depth is
+ * sdfhip_instances_penetration's (below), on sdfhip_scene_distance's exact field: this call at a coarse depth, then that one on the
+ * record's box at a finer pitch.
  * The exact skip (on by default).  b_k = (-0.5625f + e) * s <= u_k as above, so b_k >= 0 implies u_k >= 0: only the points with
  * !(b_k >= 0) look instance k up, and a 4 x 4 x 4 block of the lattice in which fewer than two instances have such a point looks
  * nothing up at all.  No margin is involved; SDFHIP_CLASH_NO_SKIP looks every instance up at every point and gives the same records.
@@ -997,6 +998,83 @@ typedef struct sdfhip_clash_stats { /* 32 bytes */
 SDFHIP_API void sdfhip_clash_options_default(sdfhip_clash_options *opt);
 SDFHIP_API int sdfhip_instances_clash(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_clash_options *opt,
                                       sdfhip_clash *out, uint32_t capacity, uint32_t *n_pairs, sdfhip_clash_stats *stats);
+
+/* ---- penetration depth: how far the overlapping pairs of an assembly reach into each other -------------
+ * Replaces: nothing in the reference's code.  sdfhip_instances_clash says THAT two parts collide, where, and in how many lattice
+ * points; this call says BY HOW MUCH and WHICH WAY TO PUSH.  It takes the same list (1..SDFHIP_CLASH_MAX_INSTANCES instances) and the
+ * same lattice, and runs one exact nearest-surface search per (point, containing part) at the points inside at least two parts.  The
+ * workflow: sdfhip_instances_clash at a coarse depth, the cube round a record's lo..hi (the bindings' clash_box), then this call on
+ * that cube at a finer pitch.  The rule, pinned (fp32, each operation rounded on its own in the order written):
+ *   lattice    sdfhip_instances_clash's, word for word: depth d in 0..10, origin[3] and side, pitch = side * 2^-d, lattice point
+ *              (x, y, z) is p_a = fmaf((float)i_a + 0.5f, pitch, origin_a), its linear index (z << 2d) | (y << d) | x
+ *   contains   sdfhip_instances_clash's, word for word: instance k contains p iff u_k(p) < 0; the ops are ignored
+ *   r_k(p)     q = the placement's inverse map of p -- the first three lines of sdfhip_scene_place's value: d = p - t,
+ *              q_a = ((R[0][a] d_0 + R[1][a] d_1) + R[2][a] d_2) * inv, inv = 1 / s, with NO clamp -- and
+ *              r_k(p) = sqrtf(d2_k(q)) * s_k, where d2_k is sdfhip_scene_distance's d2 on instance k's source at full detail
+ *              (level -1): the minimum of tri_dist2 over sdfhip_scene_mesh's triangles, a NaN never wins, an empty surface gives
+ *              +inf.  r_k is unsigned: no sign function is involved, containment is the clash rule's
+ *   depth      depth(a, b) = the maximum of fminf(r_a(p), r_b(p)) over the lattice points both contain: the radius of the largest ball,
+ *              centred on a shared lattice point, that stays inside both parts
+ *   witness    the lowest linear index attaining depth(a, b)
+ *   record     one 64-byte sdfhip_penetration for every pair a < b that shares at least one lattice point, in (a, b) order: points
+ *              (equal to the clash record's), witness, depth, ra = r_a and rb = r_b at the witness (depth = fminf(ra, rb)), node_a /
+ *              node_b = the cut cells holding the nearest triangles (as sdfhip_clearance.node), nearest_a / nearest_b = the nearest
+ *              surface points of each part in world coordinates: the search's q - r (of the triangles that tie the lowest (node,
+ *              tri) wins) mapped forward as ((R[i][0] x + R[i][1] y) + R[i][2] z) * s + t_i.  nearest_a - nearest_b is the translation
+ *              of part b that separates the pair to first order, of length about ra + rb
+ *   +inf       a depth (or ra, rb) of +inf means a part with no surface at all -- a full solid; that side's node and nearest are 0
+ *   integers   the maximum with its lowest-index tie rule does not depend on order, and it is accumulated with integer atomics only:
+ *              a 64-bit atomic max of the key (float bits << 32) | (0xFFFFFFFF - index) -- the values are >= 0 and never a NaN, so
+ *              their bits are monotone -- and an integer atomic add for points.  Two calls give the same bytes
+ * The exact skip (on by default) is sdfhip_instances_clash's; SDFHIP_PENETRATION_NO_SKIP looks every instance up at every point and
+ * gives the same records.  opt: NULL = the defaults (depth 6, origin 0, side 1, the skip on); sdfhip_penetration_options_default sets
+ * them and the size, and the struct has sdfhip_clash_options' layout and grows like it.  out receives the first min(capacity, total)
+ * records and *n_pairs the total; out may be NULL with capacity 0 (count first, then fetch).  One instance is a success with 0 pairs.
+ * stats (may be NULL): points, blocks, blocks_looked and lookups as sdfhip_clash_stats counts them; searches = the sum over the points
+ * inside two or more parts of the number of parts containing them; visited = the node records those searches loaded (the searches
+ * at the witnesses, two per record, are not counted) -- both are the same on every call; pass_ms = the device time of the count,
+ * the bitmaps, the emit, the searches, the fold and the records, kernel_ms their sum, total_ms the whole call on the host.
+ * Synchronous, on a stream of the call's own.  Every source is untouched and may be freed as soon as the call returns.
+ * SDFHIP_ERR_ARG: what sdfhip_instances_clash refuses, word for word, and more than 2^32 - 1 searches (the message names the count and
+ * says to narrow the box); SDFHIP_ERR_BAD_TREE: a source sdfhip_scene_mesh refuses, raised only when a search would run on it;
+ * SDFHIP_ERR_NOMEM: out of device memory (nothing is written, nothing leaks); SDFHIP_ERR_DEVICE as elsewhere.  Device memory: 16 bytes
+ * per search, 4 bytes per 32 nodes of each distinct searched source, 80 bytes per pair of the list.  Measured on an MI355X
+ * (profiles/penetration_bench.json), 2 / 8 / 32 overlapping instances of a 28 M-node scene and a 39 k-node torus, on a
+ * clash record's box at depths 5 and 6 (424 .. 10 306 searches): the call 3.9 .. 8.4 ms, of which the searches 1.6 .. 5.9 ms (the
+ * latency of the slowest wave: eight times the searches cost 1.1 .. 1.4 x) and the large scene's bitmap 0.67 ms, against 22 .. 843 ms
+ * for one sdfhip_scene_distance_device call per instance on all the box's points and the pairing of their values.
+ * Out of scope: the gap between DISJOINT parts (it needs searches at points in neither part and a pruning bound of its own), and
+ * lists of more than 64 instances. */
+enum { SDFHIP_PENETRATION_NO_SKIP = 1 }; /* sdfhip_penetration_options.flags: look every instance up at every lattice point */
+typedef struct sdfhip_penetration_options {
+    uint32_t size, flags;           /* sizeof(sdfhip_penetration_options) of the caller's header; SDFHIP_PENETRATION_* */
+    uint32_t depth;                 /* 0..10: 2^depth lattice points along each axis */
+    float origin[3];                /* the cube's corner */
+    float side;                     /* the cube's side: finite and above 0 */
+} sdfhip_penetration_options;       /* 28 bytes */
+typedef struct sdfhip_penetration { /* 64 bytes: one pair of instances that share lattice points */
+    uint32_t a, b;                  /* a < b: indices in the list */
+    uint32_t points;                /* >= 1: the lattice points inside both */
+    uint32_t witness;               /* the lowest linear index attaining depth */
+    float depth;                    /* the maximum over those points of fminf(r_a, r_b) */
+    float ra, rb;                   /* r_a and r_b at the witness */
+    uint32_t node_a, node_b;        /* the cut cells of the nearest triangles, in each part's source */
+    float nearest_a[3];             /* part a's nearest surface point to the witness, world coordinates */
+    float nearest_b[3];             /* part b's */
+    uint32_t pad_;
+} sdfhip_penetration;
+typedef struct sdfhip_penetration_stats { /* 72 bytes */
+    uint64_t points;                /* 8^depth */
+    uint32_t blocks, blocks_looked; /* 4 x 4 x 4 blocks of the lattice; those that looked anything up */
+    uint64_t lookups;               /* (point, instance) look-ups made, counted once */
+    uint64_t searches;              /* (point, containing instance) searches at the points inside two or more parts */
+    uint64_t visited;               /* node records those searches loaded */
+    float kernel_ms, total_ms;      /* the kernels on the device; the whole call on the host */
+    float pass_ms[6];               /* count, bitmaps, emit, searches, fold, records */
+} sdfhip_penetration_stats;
+SDFHIP_API void sdfhip_penetration_options_default(sdfhip_penetration_options *opt);
+SDFHIP_API int sdfhip_instances_penetration(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_penetration_options *opt,
+                                            sdfhip_penetration *out, uint32_t capacity, uint32_t *n_pairs, sdfhip_penetration_stats *stats);
 
 /* ---- components: the separate solids and enclosed voids of a scene, in one call ----------------------------
  * Replaces: nothing in the reference's code.  The questions of whoever has just carved, subtracted, offset, shelled or scanned: did

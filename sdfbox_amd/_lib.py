@@ -52,6 +52,7 @@ QUERY_HIT, QUERY_ESCAPED, QUERY_EXHAUSTED, QUERY_INVALID = 0, 1, 2, 3      # sdf
 INSTANCES_NO_SKIP = 1                # sdfhip_instances_options.flags: look every instance up at every point
 CLASH_NO_SKIP = 1                    # sdfhip_clash_options.flags: look every instance up at every lattice point
 CLASH_MAX_INSTANCES = 64             # sdfhip_instances_clash: a containment mask is one 64-bit word
+PENETRATION_NO_SKIP = 1              # sdfhip_penetration_options.flags: look every instance up at every lattice point
 COMPONENT_SOLID = 1                  # sdfhip_component.flags: a component of the inside phase (0: a void)
 COMPONENTS_MAX_DEPTH = 9             # sdfhip_scene_components: 4 bytes per lattice point
 # sdfhip_select_options.flags: the rule bits of sdfhip_scene_select, OR-ed
@@ -61,7 +62,7 @@ SELECT_KEEP_LARGEST_SOLID, SELECT_DROP_SMALL_SOLIDS, SELECT_FILL_ENCLOSED_VOIDS,
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, ComponentsOptions, Component, ComponentsStats, SelectOptions, SelectStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, PenetrationOptions, Penetration, PenetrationStats, ComponentsOptions, Component, ComponentsStats, SelectOptions, SelectStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -405,6 +406,35 @@ else:
     assert (ctypes.sizeof(ClashOptions), ctypes.sizeof(Clash), ctypes.sizeof(ClashStats)) == (28, 64, 32)
 
 
+    class PenetrationOptions(ctypes.Structure):
+        """sdfhip_penetration_options: flags PENETRATION_NO_SKIP or 0; depth 0..10 (2^depth lattice points along each axis); the cube's
+        origin and side (finite, above 0).  sdfhip_clash_options' layout."""
+        _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("depth", ctypes.c_uint32), ("origin", ctypes.c_float * 3),
+                    ("side", ctypes.c_float)]
+
+        def __init__(self, flags=0, depth=6, origin=(0.0, 0.0, 0.0), side=1.0):
+            super().__init__(ctypes.sizeof(type(self)), int(flags), int(depth), (ctypes.c_float * 3)(*[float(x) for x in origin]), float(side))
+
+
+    class Penetration(ctypes.Structure):
+        """sdfhip_penetration: one pair a < b of instances that share lattice points, how far they reach into each other and where
+        each part's nearest surface lies (sdfhip_instances_penetration)."""
+        _fields_ = [("a", ctypes.c_uint32), ("b", ctypes.c_uint32), ("points", ctypes.c_uint32), ("witness", ctypes.c_uint32),
+                    ("depth", ctypes.c_float), ("ra", ctypes.c_float), ("rb", ctypes.c_float), ("node_a", ctypes.c_uint32),
+                    ("node_b", ctypes.c_uint32), ("nearest_a", ctypes.c_float * 3), ("nearest_b", ctypes.c_float * 3), ("pad_", ctypes.c_uint32)]
+
+
+    class PenetrationStats(ctypes.Structure):
+        """sdfhip_penetration_stats: the clash check's counts, the searches run and the node records they loaded; pass_ms = the count,
+        the bitmaps, the emit, the searches, the fold, the records."""
+        _fields_ = [("points", ctypes.c_uint64), ("blocks", ctypes.c_uint32), ("blocks_looked", ctypes.c_uint32), ("lookups", ctypes.c_uint64),
+                    ("searches", ctypes.c_uint64), ("visited", ctypes.c_uint64), ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
+                    ("pass_ms", ctypes.c_float * 6)]
+
+
+    assert (ctypes.sizeof(PenetrationOptions), ctypes.sizeof(Penetration), ctypes.sizeof(PenetrationStats)) == (28, 64, 72)
+
+
     class ComponentsOptions(ctypes.Structure):
         """sdfhip_components_options: flags 0; depth 0..9 (2^depth lattice points along each axis); the cube's origin and side
         (finite, above 0)."""
@@ -659,6 +689,9 @@ _SIG = {
     "sdfhip_clash_options_default": (None, [_c.POINTER(ClashOptions)]),
     "sdfhip_instances_clash": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(ClashOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32),
                                           _c.POINTER(ClashStats)]),
+    "sdfhip_penetration_options_default": (None, [_c.POINTER(PenetrationOptions)]),
+    "sdfhip_instances_penetration": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(PenetrationOptions), _vp, _c.c_uint32,
+                                                _c.POINTER(_c.c_uint32), _c.POINTER(PenetrationStats)]),
     "sdfhip_components_options_default": (None, [_c.POINTER(ComponentsOptions)]),
     "sdfhip_scene_components": (_c.c_int, [_vp, _c.POINTER(ComponentsOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp,
                                            _c.POINTER(ComponentsStats)]),

@@ -168,6 +168,12 @@ def clash_box(rec, depth, origin=(0.0, 0.0, 0.0), side=1.0):
     return tuple(float(c) for c in centre - cube * 0.5), cube
 
 
+def penetration_push(rec):
+    """nearest_a - nearest_b (3,) of a penetration record (Scene.PenetrationParts): the translation of part b that separates the pair
+    to first order, of length about ra + rb.  For two overlapping balls it is the axis of their centres, from a to b."""
+    return np.asarray(rec["nearest_a"], dtype=np.float64) - np.asarray(rec["nearest_b"], dtype=np.float64)
+
+
 def component_volume(rec, depth, side=1.0):
     """The volume of a component record on the lattice of Scene.Components(depth=depth, side=side): points * pitch^3."""
     return int(rec["points"]) * (float(side) * 2.0 ** -int(depth)) ** 3
@@ -433,6 +439,27 @@ class Scene:
         n = ctypes.c_uint32()
         out = np.zeros(len(arr) * (len(arr) - 1) // 2, dtype=np.dtype(_lib.Clash))
         check(lib.sdfhip_instances_clash(arr, len(arr), ctypes.byref(opt), out.ctypes.data if len(out) else None, len(out), ctypes.byref(n), ctypes.byref(st)))
+        return out[:n.value].copy(), st
+
+    @staticmethod
+    def PenetrationParts(parts, depth=6, origin=(0.0, 0.0, 0.0), side=1.0, skip=True):
+        """The penetration depth (sdfhip_instances_penetration): how far each overlapping pair of the parts reaches into the other, on
+        ClashParts' lattice -- the 8^depth cell centres of the cube (origin, side), depth 0..10 -- and ClashParts' list.  At every
+        lattice point inside two or more parts one exact nearest-surface search runs per containing part: r_k = the distance from
+        the point to part k's surface.  Returns (records, stats): a structured array of sdfhip_penetration records in (a, b) order --
+        points as ClashParts counts them, depth = the largest fminf(r_a, r_b) over the shared points (the radius of the largest ball
+        round a shared lattice point inside both), witness = the lowest linear index attaining it, ra / rb there, node_a / node_b the
+        cut cells of the nearest triangles and nearest_a / nearest_b each part's nearest surface point in world coordinates -- and a
+        PenetrationStats.  penetration_push() reads the way to push part b.  Two calls give the same bytes.  The workflow: ClashParts
+        at a coarse depth, clash_box(record, ...) for the cube round one overlap, then PenetrationParts(parts, depth, *box) on that
+        cube at a finer pitch.  Nothing is built and nothing is kept."""
+        _, arr = Scene._instances("PenetrationParts", parts)
+        opt = _lib.PenetrationOptions(0 if skip else _lib.PENETRATION_NO_SKIP, depth, np.asarray(origin, dtype=np.float32).reshape(3).tolist(), side)
+        st = _lib.PenetrationStats()
+        n = ctypes.c_uint32()
+        out = np.zeros(len(arr) * (len(arr) - 1) // 2, dtype=np.dtype(_lib.Penetration))
+        check(lib.sdfhip_instances_penetration(arr, len(arr), ctypes.byref(opt), out.ctypes.data if len(out) else None, len(out), ctypes.byref(n),
+                                               ctypes.byref(st)))
         return out[:n.value].copy(), st
 
     @classmethod
