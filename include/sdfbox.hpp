@@ -330,6 +330,21 @@ public:
         out.resize(n);
         return out;
     }
+    // The clearance (sdfhip_instances_gap; nothing in the reference corresponds): how far apart the surfaces of each pair of the parts
+    // lie and where they are nearest, on ClashParts' list (opt: limit, SDFHIP_GAP_NO_PRUNE; null = limit +inf).  One record per pair
+    // a < b whose gap is <= limit, in (a, b) order: gap, flags, the cut cells and the two closest points in world coordinates
+    // (point_b - point_a is the way across the gap) -- the same records on every call.  The vertex-to-surface distance both ways round:
+    // never below the distance between the two meshes, above it by less than half an edge of the finer one.  stats (may be null).
+    // No model is touched
+    static std::vector<sdfhip_gap> GapParts(const std::vector<Part> &parts, const sdfhip_gap_options *opt = nullptr, sdfhip_gap_stats *stats = nullptr)
+    {
+        const std::vector<sdfhip_instance> list = InstanceList(parts, "GapParts");
+        std::vector<sdfhip_gap> out(list.size() * (list.size() ? list.size() - 1 : 0) / 2);
+        uint32_t n = 0;
+        Check(sdfhip_instances_gap(list.data(), (uint32_t)list.size(), opt, out.empty() ? nullptr : out.data(), (uint32_t)out.size(), &n, stats));
+        out.resize(n);
+        return out;
+    }
     // The components of the loaded model (sdfhip_scene_components; nothing in the reference corresponds): its face-connected solids
     // and voids on the lattice of 8^depth cell centres of the cube (opt: depth 0..9, origin, side; null = depth 6 on the unit cube).
     // One record per component in ascending label order -- label = its lowest linear index, flags = SDFHIP_COMPONENT_SOLID or 0 for a

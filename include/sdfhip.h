@@ -1043,8 +1043,8 @@ SDFHIP_API int sdfhip_instances_clash(const sdfhip_instance *instances, uint32_t
  * clash record's box at depths 5 and 6 (424 .. 10 306 searches): the call 3.9 .. 8.4 ms, of which the searches 1.6 .. 5.9 ms (the
  * latency of the slowest wave: eight times the searches cost 1.1 .. 1.4 x) and the large scene's bitmap 0.67 ms, against 22 .. 843 ms
  * for one sdfhip_scene_distance_device call per instance on all the box's points and the pairing of their values.
- * Out of scope: the gap between DISJOINT parts (it needs searches at points in neither part and a pruning bound of its own), and
- * lists of more than 64 instances. */
+ * Out of scope: the gap between DISJOINT parts, which is sdfhip_instances_gap's (below), and lists of more than 64 instances
+ * (DESIGN.md section 9). */
 enum { SDFHIP_PENETRATION_NO_SKIP = 1 }; /* sdfhip_penetration_options.flags: look every instance up at every lattice point */
 typedef struct sdfhip_penetration_options {
     uint32_t size, flags;           /* sizeof(sdfhip_penetration_options) of the caller's header; SDFHIP_PENETRATION_* */
@@ -1075,6 +1075,90 @@ typedef struct sdfhip_penetration_stats { /* 72 bytes */
 SDFHIP_API void sdfhip_penetration_options_default(sdfhip_penetration_options *opt);
 SDFHIP_API int sdfhip_instances_penetration(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_penetration_options *opt,
                                             sdfhip_penetration *out, uint32_t capacity, uint32_t *n_pairs, sdfhip_penetration_stats *stats);
+
+/* ---- clearance: how far apart the parts of an assembly are that do not overlap, and where they are nearest --
+ * Replaces: nothing in the reference's code.  sdfhip_instances_clash and sdfhip_instances_penetration answer for parts that overlap;
+ * this call answers the question asked before two parts touch.  It takes the same list (1..SDFHIP_CLASH_MAX_INSTANCES instances, the
+ * ops ignored) and returns one 64-byte record per pair a < b whose surfaces lie within `limit` of each other.  The rule, pinned (fp32,
+ * each operation rounded on its own in the order written):
+ *   surface    the surface of part k is the triangles sdfhip_scene_mesh emits for its source at full detail (level -1), in emitted
+ *              order: node ascending, then triangle k of the cell, then vertex v of the triangle
+ *   vertex     the world vertex of an emitted position (x, y, z) of part k is w_i = ((R[i][0] x + R[i][1] y) + R[i][2] z) * s + t_i, the
+ *              forward map of sdfhip_penetration's nearest points
+ *   r_k(w)     sdfhip_instances_penetration's r_k, word for word: q = the placement's inverse map of w with no clamp, and
+ *              r_k(w) = sqrtf(d2_k(q)) * s_k with d2_k sdfhip_scene_distance's d2 on instance k's source at level -1
+ *   candidates of pair (a, b): direction 0 is every vertex of a's triangles held against b, r_b(w); direction 1 every vertex of b's
+ *              triangles held against a, r_a(w)
+ *   gap        gap(a, b) = the minimum of r over all candidates.  A NaN never wins.  A pair whose minimum is +inf -- a part without
+ *              a surface, values that overflow -- has no record.  A pair has a record iff gap <= limit
+ *   witness    of the candidates attaining the minimum, the lowest (direction, node, 3 k + v)
+ *   record     a, b, gap, flags; node_a / node_b = the cut cells that hold the two closest points: on the witness's side the vertex's
+ *              cell, on the other side the cell of the nearest triangle (as sdfhip_clearance.node); corner = 3 k + v of the witness;
+ *              point_a / point_b in world coordinates: on the witness's side the witness vertex w, on the other side the search's
+ *              q - r (of the triangles that tie the lowest (node, tri) wins) mapped forward.  point_b - point_a is the bindings'
+ *              gap_vector: the way from a to b across the gap.  Records come in (a, b) order
+ *   flags      SDFHIP_GAP_WITNESS_OF_B (bit 0): the witness vertex belongs to b (direction 1).  SDFHIP_GAP_CONTAINED (bit 1): by
+ *              sdfhip_instances_clash's `contains` rule the other part contains the witness vertex, or the witness's part contains
+ *              the other side's point (two look-ups) -- the surfaces are nested or interpenetrating, and the gap is the distance
+ *              between them INSIDE a part: run sdfhip_instances_clash
+ *   integers   the minimum with its tie rule does not depend on order: a 64-bit integer atomic min of the key (float bits << 32) |
+ *              (direction << 31 | node) -- the values are >= 0 and never a NaN, so their bits are monotone, and node indices fit 31
+ *              bits because links are int32 -- from the start (bits(limit) << 32) | 0xFFFFFFFF; corner is resolved from the witness
+ *              cell alone.  Two calls give the same records
+ * What the value is.  This is the VERTEX-TO-SURFACE distance, both ways round: the closest approach of a vertex of one part's
+ * triangles to the other part's triangles.  The edge-to-edge configuration -- two edges crossing at a distance with all four end
+ * points farther away -- is not searched.  The value is therefore never below the distance between the two triangle sets, and it
+ * exceeds that distance by at most half the shorter of the two edges involved, which is less than sqrt(3) / 2 * s * 2^-depth of the
+ * finer cell (an edge of a cell's triangles lies inside the cell).
+ * opt: NULL = the defaults (limit +inf, pruning on); sdfhip_gap_options_default sets them and the size, and the struct grows like
+ * sdfhip_instances_options.  limit is in [0, +inf]; SDFHIP_GAP_NO_PRUNE runs every candidate of every pair with no bound and no broad
+ * phase and gives the same records.  out receives the first min(capacity, total) records and *n_pairs the total; out may be NULL with
+ * capacity 0 (count first, then fetch).  One instance is a success with 0 pairs.
+ * How it runs.  Per distinct source the cut cells are listed once; the host drops a pair only when the parts' bounding spheres are
+ * provably more than `limit` apart; one lane per (ordered pair, cut cell) searches from the cell's cut vertices into the other part,
+ * each search starting from the pair's best gap so far (a box is pruned only when strictly farther, so ties at the bound are found).
+ * stats (may be NULL): pairs = K (K - 1) / 2; pairs_searched = the pairs the broad phase kept, both of whose parts have a surface;
+ * cells = the (ordered pair, cut cell) lanes; searches = the vertex searches those lanes ran and visited = the node records they
+ * loaded -- BOTH DEPEND ON THE ORDER IN WHICH WAVES TIGHTEN THE BOUND AND DIFFER FROM CALL TO CALL (the records do not); under
+ * SDFHIP_GAP_NO_PRUNE they are fixed, and searches is the sum over the ordered pairs with two non-empty surfaces of 3 x the triangles
+ * of the first part.  The searches of the record pass are not counted.  pass_ms = the device time of the cell lists (the host's two
+ * waits included), the bitmaps, the searches and the records; kernel_ms their sum; total_ms the whole call on the host.
+ * Synchronous, on a stream of the call's own.  Every source is untouched and may be freed as soon as the call returns.
+ * SDFHIP_ERR_ARG: what sdfhip_instances_clash refuses of the list and of an instance, word for word, a size the growth rule refuses,
+ * unknown flags, a limit that is a NaN or negative, more than 2^31 - 1 workgroups; SDFHIP_ERR_BAD_TREE: a source sdfhip_scene_mesh
+ * refuses, raised only when a search would run on it or from it (the message names the instance): such a source has no box the
+ * broad phase could trust, so every pair of it with two surfaces is kept whatever the limit, and the call refuses it; SDFHIP_ERR_NOMEM: out of device
+ * memory (nothing is written, nothing leaks); SDFHIP_ERR_DEVICE as elsewhere.  Device memory: per distinct source 16 bytes per cut
+ * cell, 4 bytes per 256 nodes and 4 bytes per 32 nodes; 8 bytes per workgroup of the work table; 72 bytes per pair of the list.
+ * Out of scope: edge-to-edge exactness, a `level` option (coarser surfaces), a reject of whole cells from
+ * their centre, and lists of more than 64 instances. */
+enum { SDFHIP_GAP_NO_PRUNE = 1 };        /* sdfhip_gap_options.flags: every candidate of every pair, no bound, no broad phase */
+enum { SDFHIP_GAP_WITNESS_OF_B = 1, SDFHIP_GAP_CONTAINED = 2 };      /* sdfhip_gap.flags */
+typedef struct sdfhip_gap_options {
+    uint32_t size, flags;           /* sizeof(sdfhip_gap_options) of the caller's header; SDFHIP_GAP_NO_PRUNE or 0 */
+    float limit;                    /* [0, +inf]: only pairs with gap <= limit have a record */
+} sdfhip_gap_options;               /* 12 bytes */
+typedef struct sdfhip_gap {         /* 64 bytes: one pair of instances whose surfaces lie within the limit */
+    uint32_t a, b;                  /* a < b: indices in the list */
+    float gap;                      /* the minimum of r over the pair's candidates */
+    uint32_t flags;                 /* SDFHIP_GAP_WITNESS_OF_B, SDFHIP_GAP_CONTAINED */
+    uint32_t node_a, node_b;        /* the cut cells that hold the two closest points, in each part's source */
+    uint32_t corner;                /* 3 k + v: the witness vertex within its cell's triangles */
+    float point_a[3];               /* the closest point on part a, world coordinates */
+    float point_b[3];               /* ... and on part b */
+    uint32_t pad_[3];
+} sdfhip_gap;
+typedef struct sdfhip_gap_stats {   /* 56 bytes */
+    uint32_t pairs, pairs_searched; /* K (K - 1) / 2; those the broad phase kept, both parts with a surface */
+    uint64_t cells;                 /* (ordered pair, cut cell) lanes */
+    uint64_t searches;              /* vertex searches run: differs from call to call unless SDFHIP_GAP_NO_PRUNE */
+    uint64_t visited;               /* node records those searches loaded: likewise */
+    float kernel_ms, total_ms;      /* the passes on the device; the whole call on the host */
+    float pass_ms[4];               /* cell lists, bitmaps, searches, records */
+} sdfhip_gap_stats;
+SDFHIP_API void sdfhip_gap_options_default(sdfhip_gap_options *opt);
+SDFHIP_API int sdfhip_instances_gap(const sdfhip_instance *instances, uint32_t n_instances, const sdfhip_gap_options *opt, sdfhip_gap *out,
+                                    uint32_t capacity, uint32_t *n_pairs, sdfhip_gap_stats *stats);
 
 /* ---- components: the separate solids and enclosed voids of a scene, in one call ----------------------------
  * Replaces: nothing in the reference's code.  The questions of whoever has just carved, subtracted, offset, shelled or scanned: did

@@ -53,6 +53,8 @@ INSTANCES_NO_SKIP = 1                # sdfhip_instances_options.flags: look ever
 CLASH_NO_SKIP = 1                    # sdfhip_clash_options.flags: look every instance up at every lattice point
 CLASH_MAX_INSTANCES = 64             # sdfhip_instances_clash: a containment mask is one 64-bit word
 PENETRATION_NO_SKIP = 1              # sdfhip_penetration_options.flags: look every instance up at every lattice point
+GAP_NO_PRUNE = 1                     # sdfhip_gap_options.flags: every candidate of every pair, no bound, no broad phase
+GAP_WITNESS_OF_B, GAP_CONTAINED = 1, 2   # sdfhip_gap.flags: the witness vertex is part b's; one closest point is inside the other part
 COMPONENT_SOLID = 1                  # sdfhip_component.flags: a component of the inside phase (0: a void)
 COMPONENTS_MAX_DEPTH = 9             # sdfhip_scene_components: 4 bytes per lattice point
 # sdfhip_select_options.flags: the rule bits of sdfhip_scene_select, OR-ed
@@ -62,7 +64,7 @@ SELECT_KEEP_LARGEST_SOLID, SELECT_DROP_SMALL_SOLIDS, SELECT_FILL_ENCLOSED_VOIDS,
 if __name__ != "sdfbox_amd._lib":
     # the package imported a second time against another flavour of the library (sdfbox_amd.lab.load()): both flavours share ONE
     # set of ctypes classes, so that a camera, a PathTrace or a Stats object made with either package is accepted by both
-    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, PenetrationOptions, Penetration, PenetrationStats, ComponentsOptions, Component, ComponentsStats, SelectOptions, SelectStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
+    from sdfbox_amd._lib import CMesh, COctData, CTriMesh, TriMeshOptions, TriMeshStats, CPoints, Edit, EditStats, PruneOptions, PruneStats, CombineOptions, CombineStats, Placement, PlaceStats, Instance, ComposeOptions, ComposeStats, InstancesOptions, PartProbe, PartHit, ClashOptions, Clash, ClashStats, PenetrationOptions, Penetration, PenetrationStats, GapOptions, Gap, GapStats, ComponentsOptions, Component, ComponentsStats, SelectOptions, SelectStats, Volume, VolumeStats, Clearance, OffsetOptions, OffsetStats, BlendOptions, BlendStats, Hit, Info, Measure, MeasureOptions, MeshOptions, MeshStats, SliceOptions, Segment, CSlice, SliceStats, MultiLink, MultiStats, PathTrace, Probe, Ray, SdfGenStats, SdfHipError, Stats, UploadOptions   # noqa: F401
 else:
     class Info(ctypes.Structure):
         """The 112-byte `Info` cbuffer (Logic.cs:407-420)."""
@@ -435,6 +437,33 @@ else:
     assert (ctypes.sizeof(PenetrationOptions), ctypes.sizeof(Penetration), ctypes.sizeof(PenetrationStats)) == (28, 64, 72)
 
 
+    class GapOptions(ctypes.Structure):
+        """sdfhip_gap_options: flags GAP_NO_PRUNE or 0; limit in [0, +inf]: only the pairs whose gap is <= limit have a record."""
+        _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("limit", ctypes.c_float)]
+
+        def __init__(self, flags=0, limit=float("inf")):
+            super().__init__(ctypes.sizeof(type(self)), int(flags), float(limit))
+
+
+    class Gap(ctypes.Structure):
+        """sdfhip_gap: one pair a < b of instances whose surfaces lie within the limit, how far apart they are and the two closest
+        points (sdfhip_instances_gap)."""
+        _fields_ = [("a", ctypes.c_uint32), ("b", ctypes.c_uint32), ("gap", ctypes.c_float), ("flags", ctypes.c_uint32),
+                    ("node_a", ctypes.c_uint32), ("node_b", ctypes.c_uint32), ("corner", ctypes.c_uint32), ("point_a", ctypes.c_float * 3),
+                    ("point_b", ctypes.c_float * 3), ("pad_", ctypes.c_uint32 * 3)]
+
+
+    class GapStats(ctypes.Structure):
+        """sdfhip_gap_stats: the pairs of the list and those searched, the (ordered pair, cut cell) lanes, the vertex searches run and
+        the node records they loaded (both differ from call to call unless GAP_NO_PRUNE); pass_ms = the cell lists, the bitmaps, the
+        searches, the records."""
+        _fields_ = [("pairs", ctypes.c_uint32), ("pairs_searched", ctypes.c_uint32), ("cells", ctypes.c_uint64), ("searches", ctypes.c_uint64),
+                    ("visited", ctypes.c_uint64), ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float), ("pass_ms", ctypes.c_float * 4)]
+
+
+    assert (ctypes.sizeof(GapOptions), ctypes.sizeof(Gap), ctypes.sizeof(GapStats)) == (12, 64, 56)
+
+
     class ComponentsOptions(ctypes.Structure):
         """sdfhip_components_options: flags 0; depth 0..9 (2^depth lattice points along each axis); the cube's origin and side
         (finite, above 0)."""
@@ -692,6 +721,9 @@ _SIG = {
     "sdfhip_penetration_options_default": (None, [_c.POINTER(PenetrationOptions)]),
     "sdfhip_instances_penetration": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(PenetrationOptions), _vp, _c.c_uint32,
                                                 _c.POINTER(_c.c_uint32), _c.POINTER(PenetrationStats)]),
+    "sdfhip_gap_options_default": (None, [_c.POINTER(GapOptions)]),
+    "sdfhip_instances_gap": (_c.c_int, [_c.POINTER(Instance), _c.c_uint32, _c.POINTER(GapOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32),
+                                        _c.POINTER(GapStats)]),
     "sdfhip_components_options_default": (None, [_c.POINTER(ComponentsOptions)]),
     "sdfhip_scene_components": (_c.c_int, [_vp, _c.POINTER(ComponentsOptions), _vp, _c.c_uint32, _c.POINTER(_c.c_uint32), _vp,
                                            _c.POINTER(ComponentsStats)]),

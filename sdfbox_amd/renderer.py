@@ -174,6 +174,12 @@ def penetration_push(rec):
     return np.asarray(rec["nearest_a"], dtype=np.float64) - np.asarray(rec["nearest_b"], dtype=np.float64)
 
 
+def gap_vector(rec):
+    """point_b - point_a (3,) of a gap record (Scene.GapParts): the way from part a's closest point to part b's, of length about
+    gap.  Moving part b by it, reversed, closes the gap to first order."""
+    return np.asarray(rec["point_b"], dtype=np.float64) - np.asarray(rec["point_a"], dtype=np.float64)
+
+
 def component_volume(rec, depth, side=1.0):
     """The volume of a component record on the lattice of Scene.Components(depth=depth, side=side): points * pitch^3."""
     return int(rec["points"]) * (float(side) * 2.0 ** -int(depth)) ** 3
@@ -460,6 +466,27 @@ class Scene:
         out = np.zeros(len(arr) * (len(arr) - 1) // 2, dtype=np.dtype(_lib.Penetration))
         check(lib.sdfhip_instances_penetration(arr, len(arr), ctypes.byref(opt), out.ctypes.data if len(out) else None, len(out), ctypes.byref(n),
                                                ctypes.byref(st)))
+        return out[:n.value].copy(), st
+
+    @staticmethod
+    def GapParts(parts, limit=float("inf"), prune=True):
+        """The clearance (sdfhip_instances_gap): how far apart the surfaces of each pair of the parts lie and where they are nearest,
+        on ClashParts' list.  Every vertex of each part's triangles (the mesh of its source at full detail, placed) is held against
+        the other part's surface by an exact nearest-surface search that starts from the pair's best gap so far.  Returns (records,
+        stats): a structured array of sdfhip_gap records in (a, b) order, one per pair whose gap is <= limit -- gap, flags
+        (GAP_WITNESS_OF_B: the closest vertex is part b's; GAP_CONTAINED: one of the two closest points lies inside the other part, the surfaces are nested or
+        interpenetrating: run ClashParts), node_a / node_b the cut cells of the two closest points, corner = 3 k + v of the witness
+        vertex in its cell, point_a / point_b the closest points in world coordinates -- and a GapStats.  gap_vector() reads the way
+        across the gap.  This is the vertex-to-surface distance both ways round: never below the distance between the two triangle
+        sets, above it by less than half an edge of the finer mesh.  prune=False runs every candidate with no bound and gives the same
+        records.  Two calls give the same records; stats.searches and stats.visited differ from call to call unless prune=False.
+        Nothing is built and nothing is kept."""
+        _, arr = Scene._instances("GapParts", parts)
+        opt = _lib.GapOptions(0 if prune else _lib.GAP_NO_PRUNE, limit)
+        st = _lib.GapStats()
+        n = ctypes.c_uint32()
+        out = np.zeros(len(arr) * (len(arr) - 1) // 2, dtype=np.dtype(_lib.Gap))
+        check(lib.sdfhip_instances_gap(arr, len(arr), ctypes.byref(opt), out.ctypes.data if len(out) else None, len(out), ctypes.byref(n), ctypes.byref(st)))
         return out[:n.value].copy(), st
 
     @classmethod
